@@ -93,13 +93,19 @@ def parse():
                          "interposer (LD_PRELOAD=tests/fake_rccl/libfake_rccl.so with PANDA_TEST_SHARED_DEVICE_RCCL=1 FAKE_RCCL_ALLOW_SHARED_DEVICE=1, tests/test_fake_rccl.py)")
     ap.add_argument("--no-c-abi-leg", action="store_true", help="N > 1: do not run the single-process C-ABI leg after the torch.distributed legs")
     ap.add_argument("--launcher-note", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the headline MSM's result of the last timed step to DIR/msm_result_affine.npy "
+                         "(float64 words of the affine point); inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--detail", default=None, help="also write the un-shortened record (every leg's full dictionary) to this file; "
                                                    "default: gpurun_out/bench_detail_n<N>.json when gpurun_out/ exists")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def cpu_baseline(sample_log_n: int) -> dict:
-    """The only place bench.py touches the oracle: as the thing timed beside the GPU, never as the thing shipped."""
+    """One of two places bench.py touches the oracle (dump_outputs is the other): as the thing timed beside the GPU, never as the thing shipped."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle as po
 
@@ -118,6 +124,21 @@ def cpu_baseline(sample_log_n: int) -> dict:
     dt16 = time.time() - t
     out["multi_thread"] = {"value": n / dt16, "unit": "points/s", "cores": 16, "seconds": round(dt16, 2)}
     return out
+
+
+def dump_outputs(path: str, result) -> None:
+    """--dump-outputs: the BN254 MSM result the timed path handed its caller in the last timed step (96 bytes: Jacobian X, Y, Z, eight
+    32-bit Montgomery limbs each), normalised to affine x, y by the CPU oracle and written as float64 words -- exact for 32-bit integers.
+    Affine, because the Jacobian representative the library returns for the same point differs from run to run."""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle as po
+
+    words = np.frombuffer(bytes(np.ascontiguousarray(result).view(np.uint8)), dtype=np.uint32)
+    assert words.size == 24, words.size
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "msm_result_affine.npy"), po.to_affine(po.BN254, words).astype(np.float64))
 
 
 class Ctx:
@@ -328,7 +349,7 @@ def single_process(args) -> dict:
             mg.msm(cfgs)
         t0 = time.perf_counter()
         for _ in range(steps):
-            mg.msm(cfgs)
+            last = mg.msm(cfgs)
         dt = time.perf_counter() - t0
         ph = [mg.phases(d) for d in range(G)]
         if from_host is not None:
@@ -356,7 +377,7 @@ def single_process(args) -> dict:
             lib.panda_msm_unregister_bases(b)
             for p in (b, sc, r):
                 free(dev, p)
-        return dt, ph
+        return dt, ph, last
 
     def ntt_leg(total_log, reps):
         g = G.bit_length() - 1
@@ -405,7 +426,9 @@ def single_process(args) -> dict:
     log_n = args.log_n
     n = 1 << log_n
     pcie = {}
-    dt, ph = msm_leg(log_n, SEED, args.warmup, args.steps, tables=not args.no_tables, from_host=pcie)
+    dt, ph, last = msm_leg(log_n, SEED, args.warmup, args.steps, tables=not args.no_tables, from_host=pcie)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     acc_ms = ph[0][3]
     achieved = BYTES_PER_POINT[0] * n / (acc_ms * 1e-3) / 1e9
     out = {
@@ -422,7 +445,7 @@ def single_process(args) -> dict:
     }
     if not args.no_config4 and G & (G - 1) == 0:
         log_per = args.config4_total_log_n - (G.bit_length() - 1)
-        dt4, ph4 = msm_leg(log_per, SEED ^ 0xC4, 1, 3)
+        dt4, ph4, _ = msm_leg(log_per, SEED ^ 0xC4, 1, 3)
         out["config4_msm_2_26"] = {"value": (1 << args.config4_total_log_n) * 3 / dt4, "unit": "points/s", "ms_per_step": dt4 / 3 * 1e3, "n_gpus": G, "scaling": "strong",
                                    "log_points_per_gpu": log_per, "device_ms_by_rank": [round(p[7], 3) for p in ph4]}
     if not args.no_ntt and G & (G - 1) == 0:
@@ -664,6 +687,8 @@ def main():
     dt = ctx.timed(step, args.warmup, args.steps)
     lib.panda_set_clock_stamps(0)
     lib.panda_msm_set_phase_timing(0)
+    if args.dump_outputs and rank == 0:  # before any untimed call overwrites prob.result
+        dump_outputs(args.dump_outputs, prob.total if world > 1 else prob.result.cpu().numpy())
 
     out = None
     if rank == 0:

@@ -52,6 +52,33 @@ def test_argument_surface(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5", "--warmup", "2", "--single-process"])
     a = b.parse()
     assert a.gpus == 8 and a.single_process and not a.loopback
+    assert a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", "out"])
+    a = b.parse()
+    assert a.steps == 7 and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            b.parse()
+
+
+def test_dump_outputs_writes_the_affine_result(tmp_path):
+    """--dump-outputs: the 96-byte Jacobian result as the caller receives it, written as its affine point in float64 words"""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle as po
+
+    b = _bench()
+    n = 64
+    bases = po.gen_bases(po.BN254, 0x5EED, n)
+    scalars = po.gen_scalars(po.F_BN254_FR, 0x5EED + 1, n)
+    jac = po.msm(po.BN254, bases, scalars, window_bits=8)
+    b.dump_outputs(str(tmp_path / "dump"), jac.view(np.uint8))
+    assert sorted(os.listdir(tmp_path / "dump")) == ["msm_result_affine.npy"]
+    got = np.load(tmp_path / "dump" / "msm_result_affine.npy")
+    assert got.dtype == np.float64 and got.shape == (16,)
+    assert (got.astype(np.uint32) == po.msm_affine(po.BN254, bases, scalars, window_bits=8)).all()
 
 
 def test_launch_ranks_starts_the_launcher_as_a_child(monkeypatch):
@@ -126,6 +153,35 @@ def test_contract_line_fits_the_drivers_record():
     assert cm["c2_msm_2_20_tables"] == 1.45 and line["roofline"]["frac"] == 0.014 and line["cpu_baseline"]["kind"] == "port"
     assert line["broken_leg"]["error"].startswith("e") and line["failed_legs"] == ["x"]
     assert not any(isinstance(v, str) and len(v) > 200 for v in json.loads(text)["config"].values())
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_on_the_gpu_box(tmp_path):
+    """`--steps` sets the timed steps of the line, and `--dump-outputs` writes the last timed step's MSM: checked against the oracle by
+    linearity (the bases are m_i * G of the seeded stream)"""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle as po
+
+    b = _bench()
+    log_n = 16
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", str(log_n),
+           "--no-cpu-baseline", "--no-ntt", "--no-config4", "--no-extra-configs", "--no-compare",
+           "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(tmp_path / "dump")]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    aff = np.load(tmp_path / "dump" / "msm_result_affine.npy")
+    assert aff.dtype == np.float64 and aff.shape == (16,)
+    scalars = po.gen_scalars(po.F_BN254_FR, b.SEED ^ 0xFFFF, 1 << log_n)
+    assert (aff.astype(np.uint32) == po.expected_from_linearity(po.BN254, b.SEED, scalars)).all()
 
 
 @pytest.mark.gpu

@@ -1,6 +1,7 @@
 """Pins the CPU oracle: reference golden vector (k13), reference parameter tables, and an
 independent pure-Python big-int implementation.  No GPU needed."""
 import hashlib
+import json
 import os
 
 import numpy as np
@@ -8,8 +9,6 @@ import pytest
 
 import oracle as po
 import pyref
-
-REF = "/root/reference/src/cuda"
 
 
 def k13_bases():
@@ -41,16 +40,14 @@ def test_field_constants_match_reference_tables():
         assert info["bits"] == mod.bit_length()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
-def test_bls12_377_tables_match_reference_text():
-    # study of the reference as text: the 32-bit-limb tables of bls12_377/paramter.cuh:23-75
-    import re
-    txt = open(f"{REF}/core/curve/bls12_377/paramter.cuh").read()
-    nums = [int(x, 16) for x in re.findall(r"0x([0-9a-fA-F]{8})\b", txt)]
+def test_bls12_377_tables_match_reference_text(golden_dir):
+    # study of the reference as text: the 32-bit-limb tables of bls12_377/paramter.cuh:23-75, kept as a fixture
+    ref = json.load(open(os.path.join(golden_dir, "ref_bls12_377_fq_tables.json")))
     fq = po.field_info(po.F_BLS377_FQ)
-    assert nums[0:12] == [int(x) for x in fq["p"]]
-    assert nums[13:25] == [int(x) for x in fq["one"]]
-    assert nums[25:37] == [int(x) for x in fq["r2"]]
+    assert [int(x, 16) for x in ref["modulus"]] == [int(x) for x in fq["p"]]
+    assert int(ref["inv"], 16) == fq["inv"]
+    assert [int(x, 16) for x in ref["one"]] == [int(x) for x in fq["one"]]
+    assert [int(x, 16) for x in ref["r2"]] == [int(x) for x in fq["r2"]]
 
 
 @pytest.mark.parametrize("fid", [0, 1, 2, 3, 4, 5])
@@ -143,10 +140,12 @@ def test_k13_golden_vector(golden_dir):
         assert (po.msm_affine(po.BN254, bases, scalars, window_bits=w) == want).all()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 def test_k13_fixture_files_equal_reference(golden_dir):
+    """the stored k13 files are byte for byte the reference's (their sha256, recorded when they were copied)"""
+    want = json.load(open(os.path.join(golden_dir, "ref_k13_sha256.json")))
     for ours, theirs in (("ref_k13_scalars.bin", "scalars.bin"), ("ref_k13_result_affine.bin", "result_affine.bin")):
-        assert open(os.path.join(golden_dir, ours), "rb").read() == open(f"{REF}/test/data/msm/k13/{theirs}", "rb").read()
+        assert hashlib.sha256(open(os.path.join(golden_dir, ours), "rb").read()).hexdigest() == want[theirs]
+    assert hashlib.sha256(k13_bases().tobytes()).hexdigest() == want["bases.bin"]
 
 
 @pytest.mark.parametrize("cid", [0, 1, 2])
