@@ -11,7 +11,7 @@
  *   Rust-side repr(C) structs        src/gpu_ffi/common.rs:40-44,89-93,134-138,160-208
  *
  * Part 2 are the four symbols the Rust side declares but the reference never defines
- * (binding.rs:14,16,54-56).  Part 3 is additive (no reference counterpart): BLS12-377 / BLS12-381 / BN254 G2 / BLS12-381 G2,
+ * (binding.rs:14,16,54-56).  Part 3 is additive (no reference counterpart): BLS12-377 / BLS12-381 / BN254 G2 / BLS12-381 G2 / BLS12-377 G2,
  * cached-base registration and tables, the in-call upload pipeline, inverse / coset / bit-reversed NTTs, multi-GPU halves and
  * synthetic-input / diagnostics entry points.
  *
@@ -171,10 +171,19 @@ panda_error panda_msm_execute_bls12_381_g2(const panda_msm_configuration exec_cf
 panda_error panda_msm_execute_bls12_381_g2_host(const panda_msm_configuration exec_cfg);
 panda_error panda_msm_combine_bls12_381_g2(const void *partials, unsigned count, panda_msm_result_coordinate_type out_type, void *result);
 
+/* BLS12-377 G2 (no counterpart in the reference): the twist y^2 = x^3 + 1/u over Fq2 = Fq[u]/(u^2+5) (-1 is a square mod this p), scalars
+ * of BLS12-377 Fr as for G1.  Wire format as for BLS12-381 G2: an Fq2 element is c0 || c1 (2 x 48 B, Montgomery form); affine base
+ * x || y = 192 B (identity <=> x == 0), result X || Y || Z = 288 B.  Curve id 6 wherever a curve id is taken (id 5 is unused and refused).
+ * Bases are not checked for membership in the order-r subgroup.  One shape of the accumulation kernel, as for BLS12-381 G2. */
+panda_error panda_msm_setup_bls12_377_g2(void);
+panda_error panda_msm_execute_bls12_377_g2(const panda_msm_configuration exec_cfg);
+panda_error panda_msm_execute_bls12_377_g2_host(const panda_msm_configuration exec_cfg);
+panda_error panda_msm_combine_bls12_377_g2(const void *partials, unsigned count, panda_msm_result_coordinate_type out_type, void *result);
+
 /* Cached bases (README.md "Supports cached bases and scalars"; init_msm, wrapper.rs:122-152): registering a device buffer
  * of 2^log_n affine bases lets the library keep its radix-converted copy between calls instead of re-deriving it in every
  * panda_msm_execute_*; the caller must not modify the buffer until panda_msm_unregister_bases.  curve: 0 BN254, 1 BLS12-377, 2 BLS12-381, 3 BN254 G2,
- * 4 BLS12-381 G2. */
+ * 4 BLS12-381 G2, 6 BLS12-377 G2. */
 panda_error panda_msm_register_bases(unsigned curve, const void *d_bases, unsigned log_n, panda_stream stream);
 panda_error panda_msm_unregister_bases(const void *d_bases);
 /* Strict staleness check of a registration: recomputes the 64-bit hash of the whole wire buffer (one streaming pass, about 0.2 ms
@@ -200,8 +209,8 @@ panda_error panda_msm_registered_info(const void *d_bases, unsigned *tables, uns
  * on h2d_stream while range r runs digits -> sort -> accumulate on exec_cfg.stream against its own rows of the registered tables; each
  * range's buckets are added into a running total on the device, which is reduced once.  Unregistered bases, or fewer than 2^16 points
  * in the first range, reduce the number of ranges, down to one copy followed by the ordinary call.  h_scalars == NULL skips the copies
- * and runs the same schedule on resident scalars.  Synchronous on return like panda_msm_execute_*; same group element.  curve: 0 .. 4
- * (BN254, BLS12-377, BLS12-381, BN254 G2, BLS12-381 G2).  Experiment switch: ranges = 0x100 | R with h_scalars == NULL runs R (a power of two) EQUAL ranges
+ * and runs the same schedule on resident scalars.  Synchronous on return like panda_msm_execute_*; same group element.  curve: 0 .. 4, 6
+ * (BN254, BLS12-377, BLS12-381, BN254 G2, BLS12-381 G2, BLS12-377 G2).  Experiment switch: ranges = 0x100 | R with h_scalars == NULL runs R (a power of two) EQUAL ranges
  * one after the other on the caller's stream (the table-footprint measurement of profiles/r05_accumulate_table_footprint.txt). */
 panda_error panda_msm_execute_from_host(unsigned curve, const panda_msm_configuration exec_cfg, const void *h_scalars, unsigned ranges, panda_stream h2d_stream);
 
@@ -372,6 +381,7 @@ panda_error panda_msm_execute_bls12_377_multi(panda_multi_gpu mg, const panda_ms
 panda_error panda_msm_execute_bls12_381_multi(panda_multi_gpu mg, const panda_msm_configuration *cfgs, void *result /* 144 B */);
 panda_error panda_msm_execute_bn254_g2_multi(panda_multi_gpu mg, const panda_msm_configuration *cfgs, void *result /* 192 B */);
 panda_error panda_msm_execute_bls12_381_g2_multi(panda_multi_gpu mg, const panda_msm_configuration *cfgs, void *result /* 288 B */);
+panda_error panda_msm_execute_bls12_377_g2_multi(panda_multi_gpu mg, const panda_msm_configuration *cfgs, void *result /* 288 B */);
 /* The same with the scalars starting on the HOST ("scalars H2D'd per shard"; replaces the staging of unit.rs:103-188, which
  * uploads before it executes): h_scalars[d] is rank d's host source (pinned memory lets the copies run beside the kernels, pageable
  * memory works), cfgs[d].scalars the device buffer it lands in.  Every device's worker runs panda_msm_execute_from_host on its shard --
@@ -386,6 +396,8 @@ panda_error panda_msm_execute_bls12_381_from_host_multi(panda_multi_gpu mg, cons
 panda_error panda_msm_execute_bn254_g2_from_host_multi(panda_multi_gpu mg, const panda_msm_configuration *cfgs, const void *const *h_scalars, unsigned ranges,
                                                        void *result);
 panda_error panda_msm_execute_bls12_381_g2_from_host_multi(panda_multi_gpu mg, const panda_msm_configuration *cfgs, const void *const *h_scalars, unsigned ranges,
+                                                           void *result);
+panda_error panda_msm_execute_bls12_377_g2_from_host_multi(panda_multi_gpu mg, const panda_msm_configuration *cfgs, const void *const *h_scalars, unsigned ranges,
                                                            void *result);
 panda_error panda_ntt_execute_bn254_multi(panda_multi_gpu mg, const panda_ntt_slab_configuration *cfgs /* n_dev */);
 panda_error panda_ntt_execute_bn254_inverse_multi(panda_multi_gpu mg, const panda_ntt_slab_configuration *cfgs);
@@ -406,7 +418,8 @@ panda_error panda_ntt_execute_bls12_381_inverse_multi_batch(panda_multi_gpu mg, 
 /* per-phase device times of rank's last MSM inside a *_multi call (the workers' panda_msm_last_phase_ms) */
 panda_error panda_multi_gpu_last_phase_ms(panda_multi_gpu mg, unsigned rank, float *ms /* PANDA_MSM_PHASES floats */);
 
-/* Synthetic inputs generated on the device; curve: 0 = BN254, 1 = BLS12-377, 2 = BLS12-381, 3 = BN254 G2, 4 = BLS12-381 G2 */
+/* Synthetic inputs generated on the device; curve: 0 = BN254, 1 = BLS12-377, 2 = BLS12-381, 3 = BN254 G2, 4 = BLS12-381 G2,
+ * 6 = BLS12-377 G2 */
 panda_error panda_gen_scalars(unsigned curve, uint64_t seed, uint64_t first, uint64_t n, void *d_out, panda_stream stream);
 panda_error panda_gen_bases(unsigned curve, uint64_t seed, uint64_t first, uint64_t n, void *d_out, panda_stream stream);
 

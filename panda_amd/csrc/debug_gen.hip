@@ -358,6 +358,24 @@ void generator_wire<Ext2<Bls381Fq>>(u32 *out, unsigned)
     }
 }
 
+// BLS12-377 G2 generator (arkworks' G2_GENERATOR; on the twist y^2 = x^3 + 1 / u over Fq[u] / (u^2 + 5) and of order r:
+// tests/pyref_bls377_g2.py), x = x0 + x1 u
+template <>
+void generator_wire<Ext2<Bls377Fq>>(u32 *out, unsigned)
+{
+    static const u32 c[4][12] = {{0x7c005196u, 0x74e3e48fu, 0xbb535402u, 0x71889f52u, 0x57db6b9bu, 0x7ea501f5u, 0x203e5031u, 0xc565f071u, 0xa3841d01u, 0xc89630a2u, 0x71c785feu, 0x018480beu},
+                                 {0x6ea16afeu, 0xb26bfefau, 0xbff76fe6u, 0x5cf89984u, 0x0799c9deu, 0xe7223eceu, 0x6651cecbu, 0x532777eeu, 0xb1b140d5u, 0x70dc5a51u, 0xe7004031u, 0x00ea6040u},
+                                 {0x09fd4ddfu, 0xf0940944u, 0x6d8c7c2eu, 0xf2cf8888u, 0xf832d204u, 0xe458c282u, 0x74b49a58u, 0xde03ed72u, 0xcbb2efb4u, 0xd960736bu, 0x5d446f7bu, 0x00690d66u},
+                                 {0x85eb8f93u, 0xd9a1cdd1u, 0x5e52270bu, 0x4279b83fu, 0xcee304c2u, 0x2463b01au, 0x3d591bf1u, 0x61ef11acu, 0x151a70aau, 0x9e549da3u, 0xd2835518u, 0x00f8169fu}};
+    for (int j = 0; j < 4; j++) {
+        Fe<Bls377Fq> t, k, x;
+        fe_const(k, Bls377Fq::K_TOINT);
+        fe_unpack(t, c[j]);
+        fe_mul(x, t, k);
+        fe_to_wire(out + 12 * j, x);
+    }
+}
+
 template <class F>
 hipError_t gen_bases(unsigned curve, u64 seed, u64 first, u64 n, void *d_out, hipStream_t stream)
 {
@@ -406,18 +424,20 @@ panda_error panda_debug_field_op(unsigned field_id, unsigned op, void *d_r, cons
 
 panda_error panda_debug_curve_op(unsigned curve, unsigned op, void *d_r, const void *d_a, const void *d_b, size_t n, panda_stream stream)
 {
-    if (op > 4 || curve > 4) return panda_error_invalid_value;
+    if (op > 4 || !panda::msm_curve_valid(curve)) return panda_error_invalid_value;
     hipStream_t s = static_cast<hipStream_t>(stream.handle);
     dim3 grid((unsigned)((n + 127) / 128)), block(128);
     if (op >= 3) {
         dim3 qgrid((unsigned)((4 * n + 127) / 128));
         if (curve == 3) hipLaunchKernelGGL(k_curve_op_quad<Ext2<Bn254Fq>>, qgrid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
         else if (curve == 4) hipLaunchKernelGGL(k_curve_op_quad<Ext2<Bls381Fq>>, qgrid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
+        else if (curve == 6) hipLaunchKernelGGL(k_curve_op_quad<Ext2<Bls377Fq>>, qgrid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
         else if (curve == 0) hipLaunchKernelGGL(k_curve_op_quad<Bn254Fq>, qgrid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
         else if (curve == 1) hipLaunchKernelGGL(k_curve_op_quad<Bls377Fq>, qgrid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
         else hipLaunchKernelGGL(k_curve_op_quad<Bls381Fq>, qgrid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
     } else if (curve == 3) hipLaunchKernelGGL(k_curve_op<Ext2<Bn254Fq>>, grid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
     else if (curve == 4) hipLaunchKernelGGL(k_curve_op<Ext2<Bls381Fq>>, grid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
+    else if (curve == 6) hipLaunchKernelGGL(k_curve_op<Ext2<Bls377Fq>>, grid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
     else if (curve == 0) hipLaunchKernelGGL(k_curve_op<Bn254Fq>, grid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
     else if (curve == 1) hipLaunchKernelGGL(k_curve_op<Bls377Fq>, grid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
     else hipLaunchKernelGGL(k_curve_op<Bls381Fq>, grid, block, 0, s, op, (u32 *)d_r, (const u32 *)d_a, (const u32 *)d_b, n);
@@ -428,11 +448,11 @@ panda_error panda_debug_curve_op(unsigned curve, unsigned op, void *d_r, const v
 
 panda_error panda_gen_scalars(unsigned curve, uint64_t seed, uint64_t first, uint64_t n, void *d_out, panda_stream stream)
 {
-    if (curve > 4) return panda_error_invalid_value;
+    if (!panda::msm_curve_valid(curve)) return panda_error_invalid_value;
     hipStream_t s = static_cast<hipStream_t>(stream.handle);
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     if (curve == 0 || curve == 3) hipLaunchKernelGGL(k_gen_scalars<Bn254Fr>, grid, block, 0, s, seed, first, n, (u32 *)d_out);
-    else if (curve == 1) hipLaunchKernelGGL(k_gen_scalars<Bls377Fr>, grid, block, 0, s, seed, first, n, (u32 *)d_out);
+    else if (curve == 1 || curve == 6) hipLaunchKernelGGL(k_gen_scalars<Bls377Fr>, grid, block, 0, s, seed, first, n, (u32 *)d_out);
     else hipLaunchKernelGGL(k_gen_scalars<Bls381Fr>, grid, block, 0, s, seed, first, n, (u32 *)d_out);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -441,14 +461,15 @@ panda_error panda_gen_scalars(unsigned curve, uint64_t seed, uint64_t first, uin
 
 panda_error panda_gen_bases(unsigned curve, uint64_t seed, uint64_t first, uint64_t n, void *d_out, panda_stream stream)
 {
-    if (curve > 4) return panda_error_invalid_value;
+    if (!panda::msm_curve_valid(curve)) return panda_error_invalid_value;
     hipStream_t s = static_cast<hipStream_t>(stream.handle);
     switch (curve) {
     case 0: return static_cast<panda_error>(gen_bases<Bn254Fq>(curve, seed, first, n, d_out, s));
     case 1: return static_cast<panda_error>(gen_bases<Bls377Fq>(curve, seed, first, n, d_out, s));
     case 2: return static_cast<panda_error>(gen_bases<Bls381Fq>(curve, seed, first, n, d_out, s));
     case 3: return static_cast<panda_error>(gen_bases<Ext2<Bn254Fq>>(curve, seed, first, n, d_out, s));
-    default: return static_cast<panda_error>(gen_bases<Ext2<Bls381Fq>>(curve, seed, first, n, d_out, s));
+    case 4: return static_cast<panda_error>(gen_bases<Ext2<Bls381Fq>>(curve, seed, first, n, d_out, s));
+    default: return static_cast<panda_error>(gen_bases<Ext2<Bls377Fq>>(curve, seed, first, n, d_out, s));
     }
 }
 

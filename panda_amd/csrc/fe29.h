@@ -80,7 +80,8 @@ struct Fe {
     u32 l[F::N];
 };
 
-// quadratic extension B[u] / (u^2 + 1) as a "field descriptor" (fe29_ext2.h): an element is c0's limbs followed by c1's.
+// quadratic extension B[u] / (u^2 - beta) as a "field descriptor" (fe29_ext2.h; beta = -1, or -5 for BLS12-377): an element is c0's
+// limbs followed by c1's.
 // Functions that are called with explicit template arguments (fe_sub, fe_neg) dispatch on IsExt2 themselves; the rest is overloaded.
 template <class B>
 struct Ext2;
@@ -632,6 +633,9 @@ PANDA_HD void fe_reduce_once(Fe<F> &a)
 //   T = l[N-1] 2^29 + l[N-2] < 2^42   against   D = P[N-1] 2^29 + P[N-2] + 1 > p / 2^(29 (N-2)),   m = floor(T floor(2^52 / D) / 2^52):
 // m <= T / D <= value / p (no overshoot), and value / p - m < (T + 1) / (D - 1) - T / D + T / 2^52 + 1 < 1 + 2^-23 + 2^-10,
 // so the result value - m p is in [0, (1 + 2^-9) p): undershoot by at most one, as for the wide path.  T C < 2^42 2^19.3 fits 64 bits.
+// BLS12-377's p has a top limb of 0 (p < 2^377 = 2^(29 (N-1))): the same two-limb estimate, D is then P[N-2] + 1 > 2^28, T < 2^9 D and
+// T C < 2^61; the undershoot beyond one is below T / D^2 + T / 2^52 < 2^-13.  What the estimate needs is D >= 2^16 and a top limb of
+// p below 2^12 (T within 2^42 for the multiply).
 // The branch is on the field's constants (if constexpr): the wide-top-limb fields compile to exactly the one-limb code.
 template <class F>
 PANDA_HD void fe_reduce_small_2p(Fe<F> &a) // the same down to [0, 2p), tight: enough wherever another reduction follows
@@ -643,10 +647,10 @@ PANDA_HD void fe_reduce_small_2p(Fe<F> &a) // the same down to [0, 2p), tight: e
         constexpr u64 C = (1ull << 52) / ((u64)F::P[N - 1] + 1);
         m = (u32)(((u64)a.l[N - 1] * C) >> 52);
     } else {
-        static_assert(F::P[N - 1] >= 1 && F::P[N - 1] < (1u << 12), "fe_reduce_small: two-limb quotient estimate needs 1 <= top limb of p < 2^12");
         constexpr u64 D = ((u64)F::P[N - 1] << LIMB_BITS) + F::P[N - 2] + 1;
+        static_assert(F::P[N - 1] < (1u << 12) && D >= (1u << 16), "fe_reduce_small: two-limb quotient estimate needs 2^16 <= D, top limb of p < 2^12");
         constexpr u64 C = (1ull << 52) / D;
-        const u64 T = ((u64)a.l[N - 1] << LIMB_BITS) | a.l[N - 2]; // a.l[N-1] < 2^13 for values below 2^9 p
+        const u64 T = ((u64)a.l[N - 1] << LIMB_BITS) | a.l[N - 2]; // a.l[N-1] < 2^13 for values below 2^9 p (2^9 for BLS12-377)
         m = (u32)((T * C) >> 52);
     }
     int64_t carry = 0;

@@ -378,17 +378,20 @@ hipError_t msm_execute_on(unsigned curve, const panda_msm_configuration &cfg, co
     case 1: return panda::msm_execute_bls377(cfg, r, tuning, g_phase_ms, stale, pipe);
     case 2: return panda::msm_execute_bls381(cfg, r, tuning, g_phase_ms, stale, pipe);
     case 3: return panda::msm_execute_bn254_g2(cfg, r, tuning, g_phase_ms, stale, pipe);
-    default: return panda::msm_execute_bls381_g2(cfg, r, tuning, g_phase_ms, stale, pipe);
+    case 4: return panda::msm_execute_bls381_g2(cfg, r, tuning, g_phase_ms, stale, pipe);
+    case 6: return panda::msm_execute_bls377_g2(cfg, r, tuning, g_phase_ms, stale, pipe);
+    default: return hipErrorInvalidValue;
     }
 }
 
-// bytes of one affine base / one result on the wire (2 / 3 coordinates of L 32-bit limbs; G2 coordinates are pairs)
-constexpr size_t kAffineBytes[5] = {64, 96, 96, 128, 192};
-constexpr size_t kResultBytes[5] = {96, 144, 144, 192, 288};
+// bytes of one affine base / one result on the wire (2 / 3 coordinates of L 32-bit limbs; G2 coordinates are pairs), by curve id; id 5 is
+// unused (a hole: panda::msm_curve_valid refuses it before any lookup)
+constexpr size_t kAffineBytes[7] = {64, 96, 96, 128, 192, 0, 192};
+constexpr size_t kResultBytes[7] = {96, 144, 144, 192, 288, 0, 288};
 
 hipError_t msm_execute(unsigned curve, const panda_msm_configuration &cfg, const panda::MsmPipeline *pipe = nullptr)
 {
-    if (cfg.log_scalars_count > 26 || !cfg.bases) return hipErrorInvalidValue;
+    if (!panda::msm_curve_valid(curve) || cfg.log_scalars_count > 26 || !cfg.bases) return hipErrorInvalidValue;
     // buffers shorter than log_scalars_count implies are refused here instead of faulting in a kernel
     const size_t n = (size_t)1 << cfg.log_scalars_count;
     if (panda::extent_too_short(cfg.bases, n * kAffineBytes[curve]) || panda::extent_too_short(cfg.scalars, n * 32) ||
@@ -420,7 +423,7 @@ hipError_t msm_execute(unsigned curve, const panda_msm_configuration &cfg, const
 
 hipError_t register_bases(unsigned curve, const void *d_bases, unsigned log_n, bool tabled, unsigned window_bits, hipStream_t s)
 {
-    if (curve > 4 || !d_bases || log_n > 26) return hipErrorInvalidValue;
+    if (!panda::msm_curve_valid(curve) || !d_bases || log_n > 26) return hipErrorInvalidValue;
     if (panda::extent_too_short(d_bases, ((size_t)1 << log_n) * kAffineBytes[curve])) return hipErrorInvalidValue;
     const unsigned fr = panda::msm_scalar_field_of(curve);
     if (const RegisteredPtr have = lookup_registered(d_bases, log_n, curve)) {
@@ -445,7 +448,8 @@ hipError_t register_bases(unsigned curve, const void *d_bases, unsigned log_n, b
               : curve == 1 ? panda::msm_build_registration_bls377(*r, s)
               : curve == 2 ? panda::msm_build_registration_bls381(*r, s)
               : curve == 3 ? panda::msm_build_registration_bn254_g2(*r, s)
-                           : panda::msm_build_registration_bls381_g2(*r, s));
+              : curve == 4 ? panda::msm_build_registration_bls381_g2(*r, s)
+                           : panda::msm_build_registration_bls377_g2(*r, s));
     std::lock_guard<std::mutex> lock(g_registry_mutex);
     // another host thread may have registered the same buffer while this one was building its tables: keep the first, drop ours
     for (const auto &have : g_registry)
@@ -605,9 +609,12 @@ panda_error panda_msm_execute_bn254_g2(const panda_msm_configuration cfg) { retu
 panda_error panda_msm_setup_bls12_381_g2(void) { return panda_success; }
 panda_error panda_msm_execute_bls12_381_g2(const panda_msm_configuration cfg) { return static_cast<panda_error>(msm_execute(4, cfg)); }
 
+panda_error panda_msm_setup_bls12_377_g2(void) { return panda_success; }
+panda_error panda_msm_execute_bls12_377_g2(const panda_msm_configuration cfg) { return static_cast<panda_error>(msm_execute(6, cfg)); }
+
 panda_error panda_msm_execute_from_host(unsigned curve, const panda_msm_configuration cfg, const void *h_scalars, unsigned ranges, panda_stream h2d_stream)
 {
-    if (curve > 4) return panda_error_invalid_value;
+    if (!panda::msm_curve_valid(curve)) return panda_error_invalid_value;
     const panda::MsmPipeline pipe{h_scalars, ranges, static_cast<hipStream_t>(h2d_stream.handle)};
     return static_cast<panda_error>(msm_execute(curve, cfg, &pipe));
 }
@@ -621,7 +628,7 @@ panda_error panda_msm_set_window_bits(unsigned window_bits)
 
 panda_error panda_msm_plain_window_plan(unsigned curve, unsigned log_n, unsigned *window_bits, unsigned *windows)
 {
-    if (curve > 4 || log_n > 26) return panda_error_invalid_value;
+    if (!panda::msm_curve_valid(curve) || log_n > 26) return panda_error_invalid_value;
     const unsigned fr = panda::msm_scalar_field_of(curve);
     const panda::WindowPlan plan = panda::make_safe_window_plan(fr, pick_window_bits(fr, log_n));
     if (window_bits) *window_bits = plan.width[0];

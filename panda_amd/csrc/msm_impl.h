@@ -89,10 +89,13 @@ hipError_t msm_build_registration_bn254_g2(MsmRegistration &r, hipStream_t s);
 hipError_t msm_execute_bls381_g2(const panda_msm_configuration &cfg, const MsmRegistration *reg, MsmTuning tuning, float *phase_ms, bool *stale,
                                  const MsmPipeline *pipe);
 hipError_t msm_build_registration_bls381_g2(MsmRegistration &r, hipStream_t s);
+hipError_t msm_execute_bls377_g2(const panda_msm_configuration &cfg, const MsmRegistration *reg, MsmTuning tuning, float *phase_ms, bool *stale,
+                                 const MsmPipeline *pipe);
+hipError_t msm_build_registration_bls377_g2(MsmRegistration &r, hipStream_t s);
 
 // scalar field of a curve id (what the digit extraction and the window plans are keyed on): BN254 G2 shares BN254's, BLS12-381 G2
-// BLS12-381's
-static constexpr inline unsigned msm_scalar_field_of(unsigned curve) { return curve == 3 ? 0u : curve == 4 ? 2u : curve; }
+// BLS12-381's, BLS12-377 G2 (id 6; id 5 is unused) BLS12-377's
+static constexpr inline unsigned msm_scalar_field_of(unsigned curve) { return curve == 3 ? 0u : curve == 4 ? 2u : curve == 6 ? 1u : curve; }
 
 } // namespace panda
 
@@ -131,6 +134,13 @@ struct CurveBls381G2 {
     typedef Ext2<Bls381Fq> Fq;
     typedef Bls381Fr Fr;
     static constexpr unsigned ID = 4;
+};
+// BLS12-377 G2: the twist y^2 = x^3 + 1 / u over Fq2 = Fq[u] / (u^2 + 5); scalars of BLS12-377 Fr, coordinates of 2 x 12 wire words
+// (affine base 192 B, result 288 B)
+struct CurveBls377G2 {
+    typedef Ext2<Bls377Fq> Fq;
+    typedef Bls377Fr Fr;
+    static constexpr unsigned ID = 6;
 };
 
 // Waves per SIMD k_accumulate is built for.  The 9-limb fields four, the 14-limb field and BN254's Fq2 two (256 registers).  Over

@@ -512,6 +512,13 @@ panda_error panda_msm_execute_bls12_381_g2_multi(panda_multi_gpu mg, const panda
                                               panda_msm_combine_bls12_381_g2));
 }
 
+panda_error panda_msm_execute_bls12_377_g2_multi(panda_multi_gpu mg, const panda_msm_configuration *cfgs, void *result)
+{
+    if (!mg.handle) return panda_error_invalid_value;
+    return static_cast<panda_error>(msm_multi(*handle_of(mg), cfgs, result, 288, [](unsigned, const panda_msm_configuration &c) { return panda_msm_execute_bls12_377_g2(c); },
+                                              panda_msm_combine_bls12_377_g2));
+}
+
 // Scalars that start on the HOST (north_star / SURVEY 8e: "scalars H2D'd per shard"; unit.rs:103-188 stages them before it executes):
 // every worker runs the in-call upload pipeline of panda_msm_execute_from_host on its own shard -- its own arena, helper stream, copy
 // stream and PCIe link -- so the G uploads run side by side and each hides behind its shard's kernels.
@@ -558,6 +565,12 @@ panda_error panda_msm_execute_bls12_381_g2_from_host_multi(panda_multi_gpu mg, c
                                                            void *result)
 {
     return msm_from_host_multi(mg, 4, 288, panda_msm_combine_bls12_381_g2, cfgs, h_scalars, ranges, result);
+}
+
+panda_error panda_msm_execute_bls12_377_g2_from_host_multi(panda_multi_gpu mg, const panda_msm_configuration *cfgs, const void *const *h_scalars, unsigned ranges,
+                                                           void *result)
+{
+    return msm_from_host_multi(mg, 6, 288, panda_msm_combine_bls12_377_g2, cfgs, h_scalars, ranges, result);
 }
 
 panda_error panda_ntt_execute_bn254_multi(panda_multi_gpu mg, const panda_ntt_slab_configuration *cfgs)

@@ -94,6 +94,10 @@ void registry_forget_allocation(const void *ptr);
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// curve ids the MSM, generator and diagnostic entry points accept: 0 BN254, 1 BLS12-377, 2 BLS12-381, 3 BN254 G2, 4 BLS12-381 G2,
+// 6 BLS12-377 G2 (5 is unused and refused everywhere)
+static constexpr inline bool msm_curve_valid(unsigned curve) { return curve <= 4 || curve == 6; }
+
 // Boundary check for caller buffers: true when `ptr` lies in an allocation made through this library (panda_malloc,
 // panda_malloc_from_pool_async: shim.hip keeps their extents) and that allocation ends before ptr + bytes.  A caller that passes a
 // buffer shorter than log_n implies (round 2: a 4 KB buffer with log_n = 10 on a 128-byte-per-point curve) would otherwise make a

@@ -94,6 +94,8 @@ ADDITIVE_SYMBOLS = [
     "panda_ntt_execute_bls12_381_bitrev_out", "panda_ntt_execute_bls12_381_inverse_bitrev_in", "panda_ntt_execute_bls12_381_coset", "panda_ntt_execute_bls12_381_coset_inverse", "panda_ntt_slab_step1_bls12_381_enqueue", "panda_ntt_slab_step2_bls12_381_enqueue", "panda_ntt_slab_inverse_step1_bls12_381_enqueue", "panda_ntt_slab_inverse_step2_bls12_381_enqueue", "panda_ntt_execute_bls12_381_multi", "panda_ntt_execute_bls12_381_inverse_multi", "panda_ntt_execute_bls12_381_multi_batch", "panda_ntt_execute_bls12_381_inverse_multi_batch",
     "panda_msm_setup_bls12_381_g2", "panda_msm_execute_bls12_381_g2", "panda_msm_execute_bls12_381_g2_host", "panda_msm_combine_bls12_381_g2",
     "panda_msm_execute_bls12_381_g2_multi", "panda_msm_execute_bls12_381_g2_from_host_multi",
+    "panda_msm_setup_bls12_377_g2", "panda_msm_execute_bls12_377_g2", "panda_msm_execute_bls12_377_g2_host", "panda_msm_combine_bls12_377_g2",
+    "panda_msm_execute_bls12_377_g2_multi", "panda_msm_execute_bls12_377_g2_from_host_multi",
 ]
 ALL_SYMBOLS = REFERENCE_SYMBOLS + RUST_ONLY_SYMBOLS + ADDITIVE_SYMBOLS
 
@@ -143,6 +145,10 @@ def load() -> C.CDLL:
         "panda_msm_combine_bls12_381_g2": [vp, u, C.c_int, vp],
         "panda_msm_execute_bls12_381_g2_multi": [PandaMultiGpu, C.POINTER(MSMConfiguration), vp],
         "panda_msm_execute_bls12_381_g2_from_host_multi": [PandaMultiGpu, C.POINTER(MSMConfiguration), C.POINTER(vp), u, vp],
+        "panda_msm_setup_bls12_377_g2": [], "panda_msm_execute_bls12_377_g2": [MSMConfiguration], "panda_msm_execute_bls12_377_g2_host": [MSMConfiguration],
+        "panda_msm_combine_bls12_377_g2": [vp, u, C.c_int, vp],
+        "panda_msm_execute_bls12_377_g2_multi": [PandaMultiGpu, C.POINTER(MSMConfiguration), vp],
+        "panda_msm_execute_bls12_377_g2_from_host_multi": [PandaMultiGpu, C.POINTER(MSMConfiguration), C.POINTER(vp), u, vp],
         "panda_msm_setup_bls12_381": [], "panda_msm_execute_bls12_381": [MSMConfiguration], "panda_msm_execute_bls12_381_host": [MSMConfiguration],
         "panda_ntt_execute_bls12_381_v1": [NttconfigurationV1], "panda_ntt_execute_bls12_381_inverse": [NttconfigurationV1],
         "panda_ntt_execute_bn254_bitrev_out": [NttconfigurationV1], "panda_ntt_execute_bn254_inverse_bitrev_in": [NttconfigurationV1],

@@ -21,6 +21,9 @@ import numpy as np
 
 from . import gpu_ffi as ffi
 
+# bytes of one Jacobian / homogeneous result by curve id (id 5 is unused)
+_MULTI_RESULT_BYTES = {0: 96, 1: 144, 2: 144, 3: 192, 4: 288, 6: 288}
+
 
 def shard_range(n_total: int, world: int, rank: int) -> tuple[int, int]:
     """Contiguous base-point range of `rank`: (first, count)."""
@@ -44,13 +47,13 @@ def allgather_partials(partial: np.ndarray, group=None, device=None) -> np.ndarr
 
 
 def combine_partials(partials: np.ndarray, curve: int = 0, coordinate_type: int = ffi.JACOBIAN) -> np.ndarray:
-    """Sum of Jacobian partials (rows of `partials`) through panda_msm_combine_*; 96 / 144 / 192 / 288 bytes out."""
+    """Sum of Jacobian partials (rows of `partials`) through panda_msm_combine_*; 96 / 144 / 192 / 288 bytes out.  curve: 0 .. 4, 6."""
     lib = ffi.load()
     p = np.ascontiguousarray(partials).view(np.uint8)
     count = p.shape[0]
     out = np.zeros(p.shape[1], dtype=np.uint8)
-    fn = (lib.panda_msm_combine_bn254, lib.panda_msm_combine_bls12_377, lib.panda_msm_combine_bls12_381, lib.panda_msm_combine_bn254_g2,
-          lib.panda_msm_combine_bls12_381_g2)[curve]
+    fn = {0: lib.panda_msm_combine_bn254, 1: lib.panda_msm_combine_bls12_377, 2: lib.panda_msm_combine_bls12_381, 3: lib.panda_msm_combine_bn254_g2,
+          4: lib.panda_msm_combine_bls12_381_g2, 6: lib.panda_msm_combine_bls12_377_g2}[curve]  # id 5 is unused
     ffi.check(fn(C.c_void_p(p.ctypes.data), count, coordinate_type, C.c_void_p(out.ctypes.data)), "SchedulingErr")
     return out
 
@@ -268,24 +271,25 @@ class MultiGpu:
 
     def msm(self, cfgs, curve: int = 0) -> np.ndarray:
         """panda_msm_execute_*_multi: base ranges on the devices, one all-gather of partials, the total on the host."""
-        assert len(cfgs) == self.n and curve in (0, 1, 2, 3, 4)  # BN254, BLS12-377, BLS12-381 (G1), BN254 G2, BLS12-381 G2
+        # BN254, BLS12-377, BLS12-381 (G1), BN254 G2, BLS12-381 G2, BLS12-377 G2 (id 5 is unused)
+        assert len(cfgs) == self.n and curve in _MULTI_RESULT_BYTES
         arr = (ffi.MSMConfiguration * self.n)(*cfgs)
-        out = np.zeros((96, 144, 144, 192, 288)[curve], dtype=np.uint8)
-        fn = (self.lib.panda_msm_execute_bn254_multi, self.lib.panda_msm_execute_bls12_377_multi, self.lib.panda_msm_execute_bls12_381_multi,
-              self.lib.panda_msm_execute_bn254_g2_multi, self.lib.panda_msm_execute_bls12_381_g2_multi)[curve]
+        out = np.zeros(_MULTI_RESULT_BYTES[curve], dtype=np.uint8)
+        fn = {0: self.lib.panda_msm_execute_bn254_multi, 1: self.lib.panda_msm_execute_bls12_377_multi, 2: self.lib.panda_msm_execute_bls12_381_multi,
+              3: self.lib.panda_msm_execute_bn254_g2_multi, 4: self.lib.panda_msm_execute_bls12_381_g2_multi, 6: self.lib.panda_msm_execute_bls12_377_g2_multi}[curve]
         ffi.check(fn(self.handle, arr, C.c_void_p(out.ctypes.data)), "SchedulingErr")
         return out
 
     def msm_from_host(self, cfgs, host_ptrs, ranges: int = 4, curve: int = 0) -> np.ndarray:
         """panda_msm_execute_*_from_host_multi: as msm(), with rank d's scalars starting at host address host_ptrs[d] (pinned or
         pageable) and crossing PCIe inside the call -- every device uploads its own shard, in `ranges` point ranges, beside its kernels."""
-        assert len(cfgs) == len(host_ptrs) == self.n and curve in (0, 1, 2, 3, 4)
+        assert len(cfgs) == len(host_ptrs) == self.n and curve in _MULTI_RESULT_BYTES
         arr = (ffi.MSMConfiguration * self.n)(*cfgs)
         hp = (C.c_void_p * self.n)(*[C.c_void_p(int(p)) for p in host_ptrs])
-        out = np.zeros((96, 144, 144, 192, 288)[curve], dtype=np.uint8)
-        fn = (self.lib.panda_msm_execute_bn254_from_host_multi, self.lib.panda_msm_execute_bls12_377_from_host_multi,
-              self.lib.panda_msm_execute_bls12_381_from_host_multi, self.lib.panda_msm_execute_bn254_g2_from_host_multi,
-              self.lib.panda_msm_execute_bls12_381_g2_from_host_multi)[curve]
+        out = np.zeros(_MULTI_RESULT_BYTES[curve], dtype=np.uint8)
+        fn = {0: self.lib.panda_msm_execute_bn254_from_host_multi, 1: self.lib.panda_msm_execute_bls12_377_from_host_multi,
+              2: self.lib.panda_msm_execute_bls12_381_from_host_multi, 3: self.lib.panda_msm_execute_bn254_g2_from_host_multi,
+              4: self.lib.panda_msm_execute_bls12_381_g2_from_host_multi, 6: self.lib.panda_msm_execute_bls12_377_g2_from_host_multi}[curve]
         ffi.check(fn(self.handle, arr, hp, ranges, C.c_void_p(out.ctypes.data)), "SchedulingErr")
         return out
 
