@@ -1,29 +1,36 @@
 #!/usr/bin/env python3
 """bench.py -- contract benchmark: BN254 MSM 2^24 points per GPU, inputs resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input: panda_msm_execute_bn254 on this rank's
 base range (2^24 points, cached bases, Jacobian output) and, for N > 1, the all-gather of the 96-byte partials over
 RCCL plus the G - 1 point additions (weak scaling: per-GPU work is fixed).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: it sets up, runs W untimed and K timed steps, writes --dump-outputs and
+prints the line.  Its figures all come from the timed steps themselves:
 
   value      whole-job MSM points/s = N * 2^24 * K / wall (max over ranks, barrier + synchronize on both sides)
   roofline   the dominant kernel (k_accumulate): algorithmic bytes per launch (96 B/point) / its
              average duration, measured with HIP events on the launch stream inside the timed region
   roofline_issue  the same kernel against the limit that actually binds it: v_mad_u64_u32 lane-operations per second
              over the measured peak of that instruction (profiles/r01_ubench_int_rates.txt)
+
+--full adds everything that takes runs of its own, measured after the headline and outside its timed region:
+  phases_ms     every phase of the headline call, from extra untimed calls with all phase timers on
   cpu_baseline  the CPU oracle (port of the reference's host-debug Pippenger, c = 16, one thread) timed on a bounded
              sample on this box's host cores; N = 1 only
-
-Secondary figures, each measured in the same run but outside the timed region of `value` (every BASELINE.json config
-gets a number the driver records):
+and the secondary figures (every BASELINE.json configuration gets a number):
   config4_msm_2_26   BN254 MSM 2^26 in total, base ranges of 2^26 / N points per rank, partials all-gathered and combined
                      (strong scaling: at N = 8 this is BASELINE config 4 as stated, 8 x 2^23)
   ntt                N = 1: BN254 NTT 2^24 forward and inverse (config 3)
   ntt_sharded        N > 1: the slab-sharded transform (step 1 -> RCCL all-to-all -> step 2), 2^24 in total (strong) and
                      2^24 per GPU (weak)
   config2_msm_2_20, config5_bls12_377_2_24_projective   N = 1
+  without_tables, pcie_inclusive, msm_2_22, ntt_bls12_377, bn254_g2_msm_2_20, config1_host_msm_2_16   N = 1
+  c_abi_single_process   N > 1: the same workloads through the single-process C entry points, in a child process
+The --no-* options drop legs of a --full run.
 """
 from __future__ import annotations
 
@@ -72,6 +79,9 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log-n", type=int, default=24, help="log2 of the points per GPU of the headline leg (contract: 24)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the phase breakdown, the CPU baselines and every secondary configuration "
+                         "(the --no-* options below drop legs of such a run); without it only the headline is measured")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ntt", action="store_true")
     ap.add_argument("--no-ntt-sweep", action="store_true", help="NTT leg: 2^24 only (profiling runs: one size per kernel in the counters)")
@@ -96,8 +106,7 @@ def parse():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write the headline MSM's result of the last timed step to DIR/msm_result_affine.npy "
                          "(float64 words of the affine point); inputs are seeded, so two builds can be compared output for output")
-    ap.add_argument("--detail", default=None, help="also write the un-shortened record (every leg's full dictionary) to this file; "
-                                                   "default: gpurun_out/bench_detail_n<N>.json when gpurun_out/ exists")
+    ap.add_argument("--detail", default=None, help="also write the un-shortened record (every leg's full dictionary) to this file")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
@@ -426,7 +435,7 @@ def single_process(args) -> dict:
     log_n = args.log_n
     n = 1 << log_n
     pcie = {}
-    dt, ph, last = msm_leg(log_n, SEED, args.warmup, args.steps, tables=not args.no_tables, from_host=pcie)
+    dt, ph, last = msm_leg(log_n, SEED, args.warmup, args.steps, tables=not args.no_tables, from_host=pcie if args.full else None)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, last)
     acc_ms = ph[0][3]
@@ -441,14 +450,15 @@ def single_process(args) -> dict:
         "roofline": {"bound": "hbm", "kernel": "k_accumulate", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                      "algorithmic_bytes_per_launch": BYTES_PER_POINT[0] * n, "kernel_ms": acc_ms},
         "device_ms_by_rank": [round(p[7], 3) for p in ph],
-        "pcie_inclusive": pcie,
     }
-    if not args.no_config4 and G & (G - 1) == 0:
+    if args.full:
+        out["pcie_inclusive"] = pcie
+    if args.full and not args.no_config4 and G & (G - 1) == 0:
         log_per = args.config4_total_log_n - (G.bit_length() - 1)
         dt4, ph4, _ = msm_leg(log_per, SEED ^ 0xC4, 1, 3)
         out["config4_msm_2_26"] = {"value": (1 << args.config4_total_log_n) * 3 / dt4, "unit": "points/s", "ms_per_step": dt4 / 3 * 1e3, "n_gpus": G, "scaling": "strong",
                                    "log_points_per_gpu": log_per, "device_ms_by_rank": [round(p[7], 3) for p in ph4]}
-    if not args.no_ntt and G & (G - 1) == 0:
+    if args.full and not args.no_ntt and G & (G - 1) == 0:
         g = G.bit_length() - 1
         res = {"exchange": f"grouped ncclSend / ncclRecv all-to-all inside panda_ntt_execute_bn254_multi ({how})", "n_gpus": G, "unit": "elements/s"}
         res["strong_2_24_total"] = dict(ntt_leg(24, 5), scaling="strong")
@@ -465,7 +475,7 @@ def c_abi_leg(args, world: int) -> dict:
     whatever happens in there, the contract line of this run is still printed."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--single-process", "--steps", str(args.steps), "--warmup", str(args.warmup),
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--single-process", "--full", "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--log-n", str(args.log_n), "--config4-total-log-n", str(args.config4_total_log_n)]
     if args.all_on_device0:
         cmd.append("--loopback")
@@ -596,12 +606,10 @@ def contract_line(full: dict) -> dict:
 
 
 def emit(full: dict, args) -> None:
-    """print the contract line; keep the un-shortened record beside it where the builder's profiling runs pick it up"""
+    """print the contract line; with --detail, keep the un-shortened record beside it"""
     if args.launcher_note:
         full["launcher"] = args.launcher_note
     path = args.detail
-    if path is None and os.path.isdir(os.path.join(ROOT, "gpurun_out")):
-        path = os.path.join(ROOT, "gpurun_out", f"bench_detail_n{full.get('n_gpus', 1)}.json")
     if path:
         try:
             with open(path, "w") as f:
@@ -692,11 +700,9 @@ def main():
 
     out = None
     if rank == 0:
-        names = [lib.panda_msm_phase_name(i).decode() for i in range(8)]
         mean = [sum(r[i] for r in acc_ms) / len(acc_ms) for i in range(8)]
         acc_kernel_ms = mean[3]  # HIP events around k_accumulate on its launch stream, inside the timed steps
         device_ms = mean[7]
-        mean = prob.all_phases()  # every phase: separate untimed calls
 
         # per timed step: [0] cycles of the slowest-clocked XCD (the one the launch waits for: the cycles the code needed), [1] 10 ns ticks,
         # [2] XCDs stamped, [3] mean cycles over the XCDs (GRBM_GUI_ACTIVE / 8 of the same launch), [4..11] per XCD
@@ -742,10 +748,12 @@ def main():
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "algorithmic_bytes_per_launch": BYTES_PER_POINT[0] * n, "kernel_ms": acc_kernel_ms,
                          "k_accumulate_mcycles": acc_mcycles, "sclk_mhz": acc_sclk_mhz},
-            "phases_ms": {nm: round(v, 4) for nm, v in zip(names, mean)},
             "device_ms_per_step": device_ms,
             "device": device_identity(ctx),
         }
+        if args.full:  # every phase: separate untimed calls
+            names = [lib.panda_msm_phase_name(i).decode() for i in range(8)]
+            out["phases_ms"] = {nm: round(v, 4) for nm, v in zip(names, prob.all_phases())}
         if world == 1:
             ref_ms = reference_model_ms(log_n)
             out["vs_reference_model"] = {"value": ref_ms / (dt / args.steps * 1e3), "kind": "model", "reference_model_ms": ref_ms,
@@ -784,33 +792,34 @@ def main():
         if rank == 0 and res is not None:
             out[name] = res
 
-    if world == 1 and not args.no_extra_configs:
+    # a plain run measures the headline alone: every leg below is --full's
+    if args.full and world == 1 and not args.no_extra_configs:
         # the millisecond-sized configurations run straight after the headline: behind the 2^26 and BLS12-377 legs (seconds of table
         # building, tens of GB of traffic) the chip's sustained clock is ~10 % lower and they would be timed on a heat-soaked GPU
         leg("config2_msm_2_20", lambda: small_config(ctx, 0, 20, ctx.ffi.JACOBIAN, 20, "BN254 MSM 2^20, Jacobian output, cached bases (BASELINE config 2)"))
         leg("msm_2_22", lambda: small_config(ctx, 0, 22, ctx.ffi.JACOBIAN, 10, "BN254 MSM 2^22, Jacobian output, cached bases (north_star sweep 2^20 ... 2^26)"))
-    if world == 1 and not args.no_ntt:
+    if args.full and world == 1 and not args.no_ntt:
         leg("ntt", lambda: ntt_figure(ctx, sweep=not args.no_ntt_sweep))  # BASELINE config 3, also millisecond-sized: before the heavy legs, for the same reason
         if not args.no_ntt_sweep:
             leg("ntt_bls12_377", lambda: ntt_figure(ctx, sweep=False, field=1))
-    if world == 1 and not args.no_compare:
+    if args.full and world == 1 and not args.no_compare:
         leg("pcie_inclusive", lambda: pcie_inclusive(ctx, prob))
         if prob.tables > 1:
             leg("without_tables", lambda: without_tables(ctx, prob, max(2, args.steps // 2)))
     prob.release()
 
-    if not args.no_config4 and world & (world - 1) == 0 and world <= 64:
+    if args.full and not args.no_config4 and world & (world - 1) == 0 and world <= 64:
         leg("config4_msm_2_26", lambda: config4(ctx, args.config4_total_log_n))
-    if not args.no_ntt and world > 1 and world & (world - 1) == 0:
+    if args.full and not args.no_ntt and world > 1 and world & (world - 1) == 0:
         leg("ntt_sharded", lambda: ntt_sharded_figure(ctx))
-    if world == 1 and not args.no_extra_configs:
+    if args.full and world == 1 and not args.no_extra_configs:
         leg("config5_bls12_377_2_24_projective",
             lambda: small_config(ctx, 1, 24, ctx.ffi.PROJECTIVE, 5, "BLS12-377 MSM 2^24 + Projective-output conversion (BASELINE config 5)"))
         leg("bn254_g2_msm_2_20", lambda: small_config(ctx, 3, 20, ctx.ffi.JACOBIAN, 5, "BN254 G2 MSM 2^20 (SURVEY 8f-4; coordinates in Fq2), Jacobian output, cached bases"))
-    if world == 1 and not args.no_cpu_baseline and rank == 0:
+    if args.full and world == 1 and not args.no_cpu_baseline and rank == 0:
         leg("config1_host_msm_2_16", lambda: config1_host(ctx))
         leg("cpu_baseline", lambda: cpu_baseline(args.cpu_sample_log_n))
-    if world > 1 and not args.no_c_abi_leg:
+    if args.full and world > 1 and not args.no_c_abi_leg:
         # the other ranks wait on the HOST (a store key, not a collective: a rank parked in an RCCL barrier would spin on its GPU)
         ctx.torch.cuda.empty_cache()
         ctx.fence()

@@ -48,7 +48,7 @@ def test_argument_surface(monkeypatch):
     b = _bench()
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = b.parse()
-    assert (a.gpus, a.steps, a.warmup, a.log_n) == (1, 10, 3, 24) and not a.single_process
+    assert (a.gpus, a.steps, a.warmup, a.log_n) == (1, 10, 3, 24) and not a.single_process and not a.full
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5", "--warmup", "2", "--single-process"])
     a = b.parse()
     assert a.gpus == 8 and a.single_process and not a.loopback
@@ -56,6 +56,9 @@ def test_argument_surface(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", "out"])
     a = b.parse()
     assert a.steps == 7 and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = b.parse()
+    assert a.full and a.no_cpu_baseline and a.detail is None
     for bad in (["--steps", "0"], ["--warmup", "-1"]):
         monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
         with pytest.raises(SystemExit):
@@ -185,6 +188,29 @@ def test_bench_dump_outputs_on_the_gpu_box(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_measures_the_headline_alone(tmp_path):
+    """without --full the run is the headline and nothing else: the contract keys and the figures of its own timed steps, no leg of
+    its own (phases, CPU baselines, secondary configurations), in the line and in the un-shortened record"""
+    import json
+    import subprocess
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log-n", "16",
+           "--detail", str(tmp_path / "detail.json")]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    line = json.loads(lines[0])
+    assert line["metric"] == "MSM points/s (BN254, 2^24)" and line["unit"] == "points/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["roofline"]["kernel_ms"] > 0 and line["configs_ms"] == {}
+    full = json.load(open(tmp_path / "detail.json"))
+    legs = {k for k, v in full.items() if isinstance(v, dict)}
+    assert {"config", "roofline", "vs_reference_model"} <= legs <= {"config", "roofline", "roofline_issue", "vs_reference_model"}, legs
+    assert "phases_ms" not in full and "failed_legs" not in full
+
+
+@pytest.mark.gpu
 def test_bench_starts_its_own_ranks_on_the_gpu_box():
     """`python bench.py --gpus 2 ...` typed WITHOUT a launcher in front (the driver's N = 1 command with another N): one contract line under
     7 KB, two ranks (gloo, both on device 0: the rehearsal of the N > 1 path on a one-GPU box), the sharded legs in configs_ms"""
@@ -192,7 +218,7 @@ def test_bench_starts_its_own_ranks_on_the_gpu_box():
     import subprocess
 
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--all-on-device0", "--steps", "1", "--warmup", "0",
-           "--log-n", "18", "--config4-total-log-n", "19", "--no-cpu-baseline"]
+           "--log-n", "18", "--config4-total-log-n", "19", "--no-cpu-baseline", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

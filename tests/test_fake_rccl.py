@@ -102,7 +102,7 @@ def test_bench_single_process_leg_over_rccl_under_the_interposer(tmp_path):
     four ranks on device 0 over the RCCL transport under the interposer: one contract line with the sharded MSM, config 4's shape and the sharded NTT legs."""
     log = str(tmp_path / "fake_rccl_bench.log")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--single-process", "--rccl-on-device0", "--steps", "1", "--warmup", "0", "--log-n", "18",
-           "--config4-total-log-n", "20", "--detail", str(tmp_path / "detail.json")]
+           "--config4-total-log-n", "20", "--full", "--detail", str(tmp_path / "detail.json")]
     env = {k: v for k, v in _child_env(log).items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
