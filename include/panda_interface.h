@@ -429,6 +429,13 @@ panda_error panda_debug_field_op(unsigned field_id, unsigned op, void *d_r, cons
 /* op 0 = Jacobian + affine (madd), 1 = Jacobian + Jacobian, 2 = double, 3 / 4 = the four-lane spellings of 1 / 2 that the MSM's
  * fix-up and bucket-reduction trees run (csrc/curve29_quad.h); Jacobian in/out */
 panda_error panda_debug_curve_op(unsigned curve, unsigned op, void *d_r, const void *d_a, const void *d_b, size_t n, panda_stream stream);
+/* The field arithmetic on INTERNAL-form limbs, with no wire conversion, so that operands can sit anywhere inside the bounds contract of
+ * csrc/fe29.h: an element is the N 29-bit limbs the kernels hold (in u32 words; 2 N for Fq2).  field id 0..5 as panda_debug_field_op,
+ * 6 / 7 / 8 = Fq2 over BN254, BLS12-381, BLS12-377 Fq.  op: the table of csrc/fe29_debug_ops.h (0 = mul, 1 = sqr, 2 = mul_add, ...,
+ * 14 = ext2_c0); inputs the op does not use may be NULL.  panda_error_invalid_value, with nothing launched, for a (field, op) pair
+ * outside the table.  Device pointers. */
+panda_error panda_debug_fe_internal(unsigned field_id, unsigned op, void *d_r, const void *d_a, const void *d_b, const void *d_c, const void *d_d, size_t n,
+                                    panda_stream stream);
 
 const char *panda_version(void);
 

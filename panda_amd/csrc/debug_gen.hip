@@ -6,6 +6,7 @@
 // panda_gen_scalars / panda_gen_bases build the SURVEY section 8d inputs directly in HBM: 2^26 bases
 // (4 GiB) cannot sensibly be generated on the host and shipped over PCIe.
 #include "curve29_quad.h"
+#include "fe29_debug_ops.h"
 #include "panda_internal.h"
 
 using namespace panda29;
@@ -140,6 +141,25 @@ __global__ void __launch_bounds__(128) k_curve_op_quad(unsigned op, u32 *__restr
 #pragma unroll
         for (int k = 0; k < 3 * L; k++) r[i * 3 * L + k] = wr[k];
     }
+}
+
+// the op table of fe29_debug_ops.h on internal-form limbs (panda_debug_fe_internal); the host twin is tests/host_check/fe29_internal_host.cpp
+template <class F>
+__global__ void __launch_bounds__(256) k_fe_internal(unsigned op, u32 *r, const u32 *a, const u32 *b, const u32 *c, const u32 *d, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fe29_debug_op<F>(op, r, a, b, c, d, i);
+}
+
+template <class F>
+hipError_t launch_fe_internal(unsigned op, u32 *r, const u32 *a, const u32 *b, const u32 *c, const u32 *d, size_t n, hipStream_t s)
+{
+    if (!fe29_debug_supported<F>(op)) return hipErrorInvalidValue;
+    if (n) hipLaunchKernelGGL(k_fe_internal<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, r, a, b, c, d, n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
 }
 
 // ---- generators: same functions of (seed, index) as oracle/gen.c
@@ -420,6 +440,28 @@ panda_error panda_debug_field_op(unsigned field_id, unsigned op, void *d_r, cons
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return static_cast<panda_error>(e);
+}
+
+panda_error panda_debug_fe_internal(unsigned field_id, unsigned op, void *d_r, const void *d_a, const void *d_b, const void *d_c, const void *d_d, size_t n,
+                                    panda_stream stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream.handle);
+    u32 *r = (u32 *)d_r;
+    const u32 *a = (const u32 *)d_a, *b = (const u32 *)d_b, *c = (const u32 *)d_c, *d = (const u32 *)d_d;
+    hipError_t e;
+    switch (field_id) {
+    case 0: e = launch_fe_internal<Bn254Fq>(op, r, a, b, c, d, n, s); break;
+    case 1: e = launch_fe_internal<Bn254Fr>(op, r, a, b, c, d, n, s); break;
+    case 2: e = launch_fe_internal<Bls377Fq>(op, r, a, b, c, d, n, s); break;
+    case 3: e = launch_fe_internal<Bls377Fr>(op, r, a, b, c, d, n, s); break;
+    case 4: e = launch_fe_internal<Bls381Fq>(op, r, a, b, c, d, n, s); break;
+    case 5: e = launch_fe_internal<Bls381Fr>(op, r, a, b, c, d, n, s); break;
+    case 6: e = launch_fe_internal<Ext2<Bn254Fq>>(op, r, a, b, c, d, n, s); break;
+    case 7: e = launch_fe_internal<Ext2<Bls381Fq>>(op, r, a, b, c, d, n, s); break;
+    case 8: e = launch_fe_internal<Ext2<Bls377Fq>>(op, r, a, b, c, d, n, s); break;
+    default: return panda_error_invalid_value;
+    }
+    return e == hipErrorInvalidValue ? panda_error_invalid_value : static_cast<panda_error>(e);
 }
 
 panda_error panda_debug_curve_op(unsigned curve, unsigned op, void *d_r, const void *d_a, const void *d_b, size_t n, panda_stream stream)

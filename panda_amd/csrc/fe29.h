@@ -598,12 +598,16 @@ PANDA_HD void fe_pack(u32 *w, const Fe<F> &a)
     }
 }
 
-// sequential carry propagation: any limbs < 2^32 -> tight (value unchanged)
+// sequential carry propagation: limb 0 < 2^32, limbs 1..N-1 <= 2^32 - 8 (a carry is at most 7 and must not wrap the limb it lands
+// on) -> tight (value unchanged)
 template <class F>
 PANDA_HD void fe_carry(Fe<F> &a)
 {
 #pragma unroll
     for (int i = 0; i < F::N - 1; i++) {
+#if defined(FE29_CHECK)
+        assert((u64)a.l[i + 1] + (a.l[i] >> LIMB_BITS) < (1ull << 32) && "fe_carry limb range");
+#endif
         a.l[i + 1] += a.l[i] >> LIMB_BITS;
         a.l[i] &= LIMB_MASK;
     }
@@ -626,7 +630,7 @@ PANDA_HD void fe_reduce_once(Fe<F> &a)
     for (int i = 0; i < N; i++) a.l[i] = borrow ? a.l[i] : d[i];
 }
 
-// limbs < 2^32, value < 2^9 p  ->  canonical [0, p), without a multiply.
+// limbs < 2^32 (limbs 1..N-1 <= 2^32 - 8: fe_carry), value < 2^9 p  ->  canonical [0, p), without a multiply.
 // The quotient is estimated with a 2^-52 fixed-point reciprocal that never overshoots and undershoots by at most one.  For a p whose top
 // limb is wide (>= 2^16: BN254, BLS12-377, BN254 Fr, ...) the estimate is taken from the top limb alone, against (top limb of p) + 1.
 // BLS12-381's p has a top limb of 13 (4 bits), where that estimate is off by up to value / (14 2^377): the top TWO limbs then,

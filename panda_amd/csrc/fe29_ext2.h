@@ -16,7 +16,7 @@
 // beta = -5 (ext2_c0): 5 t1 of a tight product t1 (< 2p, limbs < 2^29) is below 10p, but its limbs reach 5 2^29 -- past the 2^31 - 4
 // fe_sub admits for a subtrahend.  c0 is therefore formed limb by limb as t0 + K p - 5 t1 with K p's limbs raised to a bias of 6 2^29
 // (ext2_kp6, K = 10 + SubMargin = 16 for BLS12-377's Fq): no limb underflows, none reaches 2^32 (tight t0 is below 2^29), the value is
-// below 18p, and fe_reduce_small_2p -- limbs < 2^32, value < 2^9 p in -- takes it without a carry pass in front.  The fields with
+// below 18p, and fe_reduce_small_2p -- limbs <= 2^32 - 8, value < 2^9 p in -- takes it without a carry pass in front.  The fields with
 // beta = -1 compile to exactly the code they had before the trait.
 #pragma once
 
@@ -104,8 +104,8 @@ PANDA_HD void ext2_c0(Fe<B> &c0, const Fe<B> &t0, const Fe<B> &t1)
     if constexpr (NR == -1) {
         fe_sub<B, 2>(c0, t0, t1); // < (2 + 2 + M) p, loose
     } else {
-        // t0 - 5 t1 + K p limb by limb, no carry pass: 5 t1 < 10p, K = 10 + M; the sum is below (2 + KEFF[K]) p and its limbs below 2^32,
-        // which is the input fe_reduce_small_2p takes (it starts with a sequential carry)
+        // t0 - 5 t1 + K p limb by limb, no carry pass: 5 t1 < 10p, K = 10 + M; the sum is below (2 + KEFF[K]) p and its limbs at most
+        // 2^32 - 8 (t0 + 6 2^29 + a limb of K p), which is the input fe_reduce_small_2p takes (it starts with a sequential carry)
         static_assert(NR == -5, "Ext2: beta = -1 or -5");
         constexpr int K = 10 + SubMargin<B>::value;
         static_assert(ext2_kp6<B, K>(B::N - 1) >= 5 * (2 * B::P[B::N - 1] + 1), "Ext2: K p too small for the top limb of 5 t1");
