@@ -214,6 +214,35 @@ panda_error panda_msm_registered_info(const void *d_bases, unsigned *tables, uns
  * one after the other on the caller's stream (the table-footprint measurement of profiles/r05_accumulate_table_footprint.txt). */
 panda_error panda_msm_execute_from_host(unsigned curve, const panda_msm_configuration exec_cfg, const void *h_scalars, unsigned ranges, panda_stream h2d_stream);
 
+/* `batch` MSMs over ONE base set in one call: the shape a prover calls an MSM in (every commitment of a round goes against the same SRS).
+ * exec_cfg is as for panda_msm_execute_*: bases = 2^log_scalars_count affine points; scalars = batch x 2^log_scalars_count x 32 B on the
+ * device, member j at byte offset j * 2^log_scalars_count * 32, read-only; results = batch x (96 / 144 / 192 / 288) B, member j at
+ * j * result bytes, device or pinned host or pageable host; msm_result_coordinate_type applies to every member.  Synchronous on return.
+ * Member j's result is the same group element as panda_msm_execute_* on member j alone; the raw bytes are ONE representative of it
+ * (Jacobian / homogeneous coordinates are defined up to a factor, and the order in which a bucket's points are added follows the wave
+ * scheduling -- true of the single call as well): compare affine points, never bytes.  curve: 0 .. 4, 6.
+ *   batch: 1 .. PANDA_MSM_MAX_BATCH.  batch == 0 or above the maximum, curve 5 or > 6, log_scalars_count > 26, NULL buffers, and scalar /
+ *     result buffers of this library's allocators that are shorter than `batch` members return panda_error_invalid_value, nothing
+ *     launched; the batch == 0 / curve / NULL checks come before any runtime call.
+ *   Bases with precomputed tables (panda_msm_precompute_bases): the FUSED path.  The batch is cut into groups of a power-of-two number of
+ *     members (13 = 8 + 4 + 1; the largest group is what panda_msm_batch_plan reports), and a group runs as one MSM of group x n scalars
+ *     whose bucket id carries the member index: one digits pass, one sort, one accumulation and one fix-up for the group, one reduction
+ *     that emits the group's results.  The tables' window plan is used as registered.
+ *   Registered without tables, or not registered: the members run one after the other through the path of the single call.
+ *   A registration found stale (sampled rows, or the hash under panda_msm_set_paranoid) is dropped and the WHOLE batch answered from the
+ *     caller's buffer, as a single call does.
+ *   The experiment setters (panda_msm_set_overlap, _accumulate_variant, _wide_merge, _chunk_first, point ranges) have no effect on the fused
+ *     path, which ships in the built-in shape of each curve; panda_msm_set_window_bits and _chunk_entries keep their meaning for the
+ *     unfused path only.  panda_msm_last_phase_ms after a fused batch reports the LAST group: its device time in "total_device" (under
+ *     panda_msm_set_phase_timing(1) or (2)), the other phases 0; after an unfused batch, the last member. */
+#define PANDA_MSM_MAX_BATCH 1024
+panda_error panda_msm_execute_batch(unsigned curve, const panda_msm_configuration exec_cfg, unsigned batch);
+/* How a batch would run (pure host arithmetic, no device call): window_bits = the window of the precomputed tables
+ * (panda_msm_registered_info), 0 = the built-in tabled policy for 2^log_n points.  *group_log = log2 of the largest number of members
+ * fused into one sort + accumulate (0: members run one after the other), *sequences = number of kernel sequences the whole batch is cut
+ * into.  Either pointer may be NULL.  Invalid: curve 5 or > 6, log_n > 26, batch 0 or > PANDA_MSM_MAX_BATCH, window_bits 1 .. 3 or > 24. */
+panda_error panda_msm_batch_plan(unsigned curve, unsigned log_n, unsigned window_bits, unsigned batch, unsigned *group_log, unsigned *sequences);
+
 /* Window size override for experiments: 0 = built-in policy (replaces get_window_bits_count, msm_cuda.cuh:21-45) */
 panda_error panda_msm_set_window_bits(unsigned window_bits);
 /* what the plain path (no precomputed tables) would run a 2^log_n-point MSM of `curve` with: widest window and number of windows */

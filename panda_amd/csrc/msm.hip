@@ -389,6 +389,21 @@ hipError_t msm_execute_on(unsigned curve, const panda_msm_configuration &cfg, co
 constexpr size_t kAffineBytes[7] = {64, 96, 96, 128, 192, 0, 192};
 constexpr size_t kResultBytes[7] = {96, 144, 144, 192, 288, 0, 288};
 
+// strict mode (panda_msm_set_paranoid): a registration whose buffer no longer hashes to what was registered is dropped
+hipError_t drop_if_hash_changed(unsigned curve, const panda_msm_configuration &cfg, RegisteredPtr &reg)
+{
+    if (!reg || !g_paranoid.load(std::memory_order_relaxed)) return hipSuccess;
+    uint64_t now = 0;
+    PANDA_TRY(panda::msm_hash_wire(cfg.bases, ((size_t)1 << cfg.log_scalars_count) * kAffineBytes[curve], static_cast<hipStream_t>(cfg.stream.handle), &now));
+    if (now != reg->hash) {
+        fprintf(stderr, "[panda-hip] registered bases at %p changed since registration (hash): registration dropped, converting per call\n", cfg.bases);
+        const RegisteredBases *gone = reg.get();
+        forget_if([gone](const RegisteredBases &r) { return &r == gone; });
+        reg.reset();
+    }
+    return hipSuccess;
+}
+
 hipError_t msm_execute(unsigned curve, const panda_msm_configuration &cfg, const panda::MsmPipeline *pipe = nullptr)
 {
     if (!panda::msm_curve_valid(curve) || cfg.log_scalars_count > 26 || !cfg.bases) return hipErrorInvalidValue;
@@ -398,16 +413,7 @@ hipError_t msm_execute(unsigned curve, const panda_msm_configuration &cfg, const
         panda::extent_too_short(cfg.results, kResultBytes[curve]))
         return hipErrorInvalidValue;
     RegisteredPtr reg = lookup_registered(cfg.bases, cfg.log_scalars_count, curve); // held for the whole call
-    if (reg && g_paranoid.load(std::memory_order_relaxed)) { // strict mode: the whole buffer must still hash to what was registered
-        uint64_t now = 0;
-        PANDA_TRY(panda::msm_hash_wire(cfg.bases, n * kAffineBytes[curve], static_cast<hipStream_t>(cfg.stream.handle), &now));
-        if (now != reg->hash) {
-            fprintf(stderr, "[panda-hip] registered bases at %p changed since registration (hash): registration dropped, converting per call\n", cfg.bases);
-            const RegisteredBases *gone = reg.get();
-            forget_if([gone](const RegisteredBases &r) { return &r == gone; });
-            reg.reset();
-        }
-    }
+    PANDA_TRY(drop_if_hash_changed(curve, cfg, reg)); // strict mode: the whole buffer must still hash to what was registered
     bool stale = false;
     hipError_t e = msm_execute_on(curve, cfg, reg.get(), &stale, pipe);
     if (e == hipSuccess && stale) {
@@ -419,6 +425,76 @@ hipError_t msm_execute(unsigned curve, const panda_msm_configuration &cfg, const
         e = msm_execute_on(curve, cfg, nullptr, nullptr, pipe);
     }
     return e;
+}
+
+// ---- batches: many scalar vectors over one base set (panda_msm_execute_batch)
+// Group policy.  A group of 2^gl members is one MSM of 2^(log_n + gl) scalars over 2^(c - 1 + gl) buckets.  It is as large as
+//   * about 2^22 scalars in all: W 2^22 sorted entries are four and more rounds of the chip's resident accumulate threads at the largest
+//     chunk size, beyond which a larger group only costs workspace;
+//   * the sort's geometry for the wider bucket id (msm_sort_tabled_batch_supported, every smaller group included: the ragged end of a
+//     batch uses them) and the 2^26-scalar index width;
+//   * a bucket array of at most 1 GiB (taken as twice the result bytes per bucket, an upper bound of the XYZZ accumulator of every curve)
+// allow.  Pure host arithmetic: panda_msm_batch_plan reports it without a device.
+constexpr unsigned kBatchGroupScalarsLog = 22;
+unsigned batch_group_log_max(unsigned curve, unsigned log_n, const panda::WindowPlan &plan)
+{
+    if (!panda::msm_sort_tabled_supported(log_n, plan)) return 0;
+    unsigned gl = 0;
+    while (log_n + gl + 1 <= kBatchGroupScalarsLog && panda::msm_sort_tabled_batch_supported(log_n, gl + 1, plan) &&
+           ((u64)(2 * kResultBytes[curve]) << (plan.width[0] - 1 + gl + 1)) <= ((u64)1 << 30))
+        gl++;
+    return gl;
+}
+
+hipError_t msm_execute_batch(unsigned curve, const panda_msm_configuration &cfg, unsigned batch)
+{
+    // (these checks come before any HIP runtime call: a machine without a device can test them)
+    if (!panda::msm_curve_valid(curve) || batch == 0 || batch > PANDA_MSM_MAX_BATCH || cfg.log_scalars_count > 26 || !cfg.bases || !cfg.scalars || !cfg.results)
+        return hipErrorInvalidValue;
+    const size_t n = (size_t)1 << cfg.log_scalars_count;
+    if (panda::extent_too_short(cfg.bases, n * kAffineBytes[curve]) || panda::extent_too_short(cfg.scalars, (size_t)batch * n * 32) ||
+        panda::extent_too_short(cfg.results, (size_t)batch * kResultBytes[curve]))
+        return hipErrorInvalidValue;
+    RegisteredPtr reg = lookup_registered(cfg.bases, cfg.log_scalars_count, curve); // held for the whole call
+    PANDA_TRY(drop_if_hash_changed(curve, cfg, reg));
+    auto forget = [&]() {
+        fprintf(stderr, "[panda-hip] registered bases at %p changed since registration: registration dropped, converting per call\n", cfg.bases);
+        const RegisteredBases *gone = reg.get();
+        forget_if([gone](const RegisteredBases &r) { return &r == gone; });
+        reg.reset();
+    };
+    if (reg && reg->tabled) {
+        const unsigned gl_max = batch_group_log_max(curve, cfg.log_scalars_count, reg->plan);
+        if (panda::msm_batch_next_group_log(batch, gl_max) >= 1) { // the fused path
+            const unsigned timing = g_phase_timing.load(std::memory_order_relaxed);
+            bool stale = false;
+            hipError_t e = hipErrorInvalidValue;
+            switch (curve) {
+            case 0: e = panda::msm_execute_batch_bn254(cfg, reg.get(), batch, gl_max, timing, g_phase_ms, &stale); break;
+            case 1: e = panda::msm_execute_batch_bls377(cfg, reg.get(), batch, gl_max, timing, g_phase_ms, &stale); break;
+            case 2: e = panda::msm_execute_batch_bls381(cfg, reg.get(), batch, gl_max, timing, g_phase_ms, &stale); break;
+            case 3: e = panda::msm_execute_batch_bn254_g2(cfg, reg.get(), batch, gl_max, timing, g_phase_ms, &stale); break;
+            case 4: e = panda::msm_execute_batch_bls381_g2(cfg, reg.get(), batch, gl_max, timing, g_phase_ms, &stale); break;
+            case 6: e = panda::msm_execute_batch_bls377_g2(cfg, reg.get(), batch, gl_max, timing, g_phase_ms, &stale); break;
+            }
+            if (e != hipSuccess || !stale) return e;
+            forget(); // and the whole batch is answered from the caller's buffer, below
+        }
+    }
+    // registered without tables, unregistered, or nothing to fuse: the members one after the other through the single call's path
+    for (unsigned j = 0; j < batch; j++) {
+        panda_msm_configuration one = cfg;
+        one.scalars = (char *)cfg.scalars + (size_t)j * n * 32;
+        one.results = (char *)cfg.results + (size_t)j * kResultBytes[curve];
+        bool stale = false;
+        hipError_t e = msm_execute_on(curve, one, reg.get(), &stale, nullptr);
+        if (e == hipSuccess && stale) {
+            forget();
+            e = msm_execute_on(curve, one, nullptr, nullptr, nullptr);
+        }
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t register_bases(unsigned curve, const void *d_bases, unsigned log_n, bool tabled, unsigned window_bits, hipStream_t s)
@@ -611,6 +687,26 @@ panda_error panda_msm_execute_bls12_381_g2(const panda_msm_configuration cfg) { 
 
 panda_error panda_msm_setup_bls12_377_g2(void) { return panda_success; }
 panda_error panda_msm_execute_bls12_377_g2(const panda_msm_configuration cfg) { return static_cast<panda_error>(msm_execute(6, cfg)); }
+
+panda_error panda_msm_execute_batch(unsigned curve, const panda_msm_configuration cfg, unsigned batch) { return static_cast<panda_error>(msm_execute_batch(curve, cfg, batch)); }
+
+panda_error panda_msm_batch_plan(unsigned curve, unsigned log_n, unsigned window_bits, unsigned batch, unsigned *group_log, unsigned *sequences)
+{
+    if (!panda::msm_curve_valid(curve) || log_n > 26 || batch == 0 || batch > PANDA_MSM_MAX_BATCH || (window_bits && (window_bits < 4 || window_bits > 24)))
+        return panda_error_invalid_value;
+    const unsigned fr = panda::msm_scalar_field_of(curve);
+    const unsigned c = window_bits ? window_bits : pick_tabled_window_bits(fr, log_n);
+    const unsigned gl_max = c ? batch_group_log_max(curve, log_n, panda::make_safe_window_plan(fr, c)) : 0u;
+    unsigned top = 0, count = 0;
+    for (unsigned done = 0; done < batch; count++) {
+        const unsigned gl = panda::msm_batch_next_group_log(batch - done, gl_max);
+        top = std::max(top, gl);
+        done += 1u << gl;
+    }
+    if (group_log) *group_log = top;
+    if (sequences) *sequences = top ? count : batch;
+    return panda_success;
+}
 
 panda_error panda_msm_execute_from_host(unsigned curve, const panda_msm_configuration cfg, const void *h_scalars, unsigned ranges, panda_stream h2d_stream)
 {

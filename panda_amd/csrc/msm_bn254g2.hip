@@ -10,6 +10,12 @@ hipError_t msm_execute_bn254_g2(const panda_msm_configuration &cfg, const MsmReg
     return msm_execute<CurveBn254G2>(cfg, reg, tuning, phase_ms, stale, pipe);
 }
 
+hipError_t msm_execute_batch_bn254_g2(const panda_msm_configuration &cfg, const MsmRegistration *reg, unsigned batch, unsigned group_log_max, unsigned timing,
+                                      float *phase_ms, bool *stale)
+{
+    return msm_execute_batch<CurveBn254G2>(cfg, reg, batch, group_log_max, timing, phase_ms, stale);
+}
+
 hipError_t msm_build_registration_bn254_g2(MsmRegistration &r, hipStream_t s) { return build_registration<Ext2<Bn254Fq>>(r, s); }
 
 } // namespace panda

@@ -93,6 +93,30 @@ hipError_t msm_execute_bls377_g2(const panda_msm_configuration &cfg, const MsmRe
                                  const MsmPipeline *pipe);
 hipError_t msm_build_registration_bls377_g2(MsmRegistration &r, hipStream_t s);
 
+// `batch` scalar vectors over ONE set of precomputed tables (panda_msm_execute_batch; reg->tabled must hold): the batch is cut into
+// groups of a power-of-two number of members, at most 2^group_log_max, each group one kernel sequence.  cfg.scalars / cfg.results hold
+// the members one after the other.  timing != 0: phase_ms[7] is the device time of the last group, the other phases read 0.
+hipError_t msm_execute_batch_bn254(const panda_msm_configuration &cfg, const MsmRegistration *reg, unsigned batch, unsigned group_log_max, unsigned timing,
+                                    float *phase_ms, bool *stale);
+hipError_t msm_execute_batch_bls377(const panda_msm_configuration &cfg, const MsmRegistration *reg, unsigned batch, unsigned group_log_max, unsigned timing,
+                                     float *phase_ms, bool *stale);
+hipError_t msm_execute_batch_bls381(const panda_msm_configuration &cfg, const MsmRegistration *reg, unsigned batch, unsigned group_log_max, unsigned timing,
+                                     float *phase_ms, bool *stale);
+hipError_t msm_execute_batch_bn254_g2(const panda_msm_configuration &cfg, const MsmRegistration *reg, unsigned batch, unsigned group_log_max, unsigned timing,
+                                       float *phase_ms, bool *stale);
+hipError_t msm_execute_batch_bls381_g2(const panda_msm_configuration &cfg, const MsmRegistration *reg, unsigned batch, unsigned group_log_max, unsigned timing,
+                                        float *phase_ms, bool *stale);
+hipError_t msm_execute_batch_bls377_g2(const panda_msm_configuration &cfg, const MsmRegistration *reg, unsigned batch, unsigned group_log_max, unsigned timing,
+                                        float *phase_ms, bool *stale);
+
+// How a batch is cut: the members left are served by the largest power-of-two group that is at most 2^group_log_max (13 = 8 + 4 + 1).
+static inline unsigned msm_batch_next_group_log(unsigned members_left, unsigned group_log_max)
+{
+    unsigned gl = 0;
+    while (gl < group_log_max && (2u << gl) <= members_left) gl++;
+    return gl;
+}
+
 // scalar field of a curve id (what the digit extraction and the window plans are keyed on): BN254 G2 shares BN254's, BLS12-381 G2
 // BLS12-381's, BLS12-377 G2 (id 6; id 5 is unused) BLS12-377's
 static constexpr inline unsigned msm_scalar_field_of(unsigned curve) { return curve == 3 ? 0u : curve == 4 ? 2u : curve == 6 ? 1u : curve; }
@@ -1021,7 +1045,8 @@ __global__ void __launch_bounds__(64) k_weighted_slots(const u32 *__restrict__ i
 
 // workgroup `list`, one wave: the list's slots * parts partial sums -> win[list] -- as an XYZZ point (emit = 0: the host still has a
 // Horner step to do over the lists), or, for a single list whose sum IS the result, in the wire format of the C ABI: Jacobian
-// X || Y || Z (emit = 1) or homogeneous (emit = 2).  `win` may be device memory or pinned host memory.
+// X || Y || Z (emit = 1) or homogeneous (emit = 2), list after list (a batch: one list per member).  `win` may be device memory or
+// pinned host memory.
 // (A kernel of its own rather than the last-to-finish workgroup of k_weighted_slots: the device-scope fences such a hand-off needs
 // write the XCD's L2 back in every workgroup -- profiles/r04_msm_small_sizes.txt -- and cost more than the launch.)
 template <class F>
@@ -1048,7 +1073,7 @@ __global__ void __launch_bounds__(64) k_slot_total(const u32 *__restrict__ slot_
             else
                 xyzz_to_jacobian_wire(out, acc);
 #pragma unroll
-            for (int k = 0; k < 3 * F::L; k++) win[k] = out[k];
+            for (int k = 0; k < 3 * F::L; k++) win[(u64)list * (3 * F::L) + k] = out[k];
         }
     }
 }
@@ -1110,6 +1135,21 @@ unsigned floor_log2(u64 v)
     return l;
 }
 
+// sorted entries per k_accumulate thread, for `entries` sorted entries over all lists: as many as leave about 2^20 threads -- six rounds
+// of the chip's 2^18 resident threads at four waves per SIMD, so neither a half-empty chip nor a half-empty last round costs much
+// (a 2^21-point range at K = 128 kept three waves per SIMD busy: 2.4 ms instead of 1.8); 64 ... 256 measure the same at 2^24
+template <class Fq>
+unsigned acc_chunk_entries(u64 entries, unsigned forced)
+{
+    const u64 per_k = entries >> 20;
+    unsigned K = per_k >= 128 ? 128 : (per_k >= 64 ? 64 : (per_k >= 32 ? 32 : 16));
+    // below 2^22 points the threads are fewer than four rounds of the chip and the best chunk is a matter of how the last round fills:
+    // interleaved sweeps (tools/chunk_sweep.py, profiles/r05_chunk_sweep.txt) put 24 in front at 2^19 (-3.4 %) and 32 at 2^20 / 2^21 (-1 %)
+    if (Fq::N <= 9 && per_k < 32) K = per_k >= 12 ? 32 : (per_k >= 6 ? 24 : 16);
+    if (forced) K = std::min(std::max((forced + 3u) & ~3u, 4u), 1024u); // multiples of four: chunks start on 16 bytes
+    return K;
+}
+
 template <class C>
 hipError_t msm_execute(const panda_msm_configuration &cfg, const panda::MsmRegistration *registration, panda::MsmTuning tuning, float *phase_ms, bool *stale,
                        const panda::MsmPipeline *pipe)
@@ -1165,15 +1205,7 @@ hipError_t msm_execute(const panda_msm_configuration &cfg, const panda::MsmRegis
     auto range_geom = [&](unsigned log_c) {
         RangeGeom g;
         g.stride = tabled ? (u64)W << log_c : (u64)1 << log_c;
-        // sorted entries per accumulate thread: as many as leave about 2^20 threads over all lists -- six rounds of the chip's
-        // 2^18 resident threads at four waves per SIMD, so neither a half-empty chip nor a half-empty last round costs much
-        // (a 2^21-point range at K = 128 kept three waves per SIMD busy: 2.4 ms instead of 1.8); 64 ... 256 measure the same at 2^24
-        const u64 per_k = ((u64)lists * g.stride) >> 20;
-        g.K = per_k >= 128 ? 128 : (per_k >= 64 ? 64 : (per_k >= 32 ? 32 : 16));
-        // below 2^22 points the threads are fewer than four rounds of the chip and the best chunk is a matter of how the last round fills:
-        // interleaved sweeps (tools/chunk_sweep.py, profiles/r05_chunk_sweep.txt) put 24 in front at 2^19 (-3.4 %) and 32 at 2^20 / 2^21 (-1 %)
-        if (Fq::N <= 9 && per_k < 32) g.K = per_k >= 12 ? 32 : (per_k >= 6 ? 24 : 16);
-        if (tuning.chunk) g.K = std::min(std::max((tuning.chunk + 3u) & ~3u, 4u), 1024u); // multiples of four: chunks start on 16 bytes
+        g.K = acc_chunk_entries<Fq>((u64)lists * g.stride, tuning.chunk);
         g.chunks = (unsigned)((g.stride + g.K - 1) / g.K);
         g.long_cap = g.chunks / LONG_SPAN + 2;
         return g;
@@ -1519,6 +1551,160 @@ hipError_t msm_execute(const panda_msm_configuration &cfg, const panda::MsmRegis
     phase_ms[6] = phase_ms[7] = 0;
     if (wanted(6) && wanted(7) && hipEventElapsedTime(&ms, ev[6], ev[7]) == hipSuccess) phase_ms[6] = ms;
     if (wanted(0) && wanted(6) && hipEventElapsedTime(&ms, ev[0], ev[6]) == hipSuccess) phase_ms[7] = ms;
+    return hipSuccess;
+}
+
+
+// panda_msm_execute_batch with precomputed tables: every group of G = 2^gl members runs as ONE MSM of G n scalars whose bucket id
+// carries the member index in its top bits (msm_sort_tabled_batch) -- one digits pass, one sort, one k_accumulate grid and one fix-up
+// over G NB buckets, all gathering from the same tables -- and a reduction with lists = G over the same array read as [G][NB], whose last
+// kernel writes the G results in wire form.  Ships in one shape, the built-in one of each curve: no overlap, point ranges or
+// accumulate variants.
+template <class C>
+hipError_t msm_execute_batch(const panda_msm_configuration &cfg, const panda::MsmRegistration *reg, unsigned batch, unsigned group_log_max, unsigned timing,
+                             float *phase_ms, bool *stale)
+{
+    typedef typename C::Fq Fq;
+    constexpr int PW = 4 * Fq::N;
+    constexpr int LQ = Fq::L;
+    constexpr unsigned fr = panda::msm_scalar_field_of(C::ID);
+    hipStream_t stream = static_cast<hipStream_t>(cfg.stream.handle);
+    const unsigned log_n = cfg.log_scalars_count;
+    if (!reg || !reg->tabled || batch == 0 || log_n > 26 || !cfg.bases || !cfg.scalars || !cfg.results) return hipErrorInvalidValue;
+    const u64 n = (u64)1 << log_n;
+    const panda::WindowPlan &plan = reg->plan;
+    const unsigned W = plan.W, c = plan.width[0], NB = 1u << (c - 1);
+    // the largest group: the first one (groups never grow along the batch)
+    const unsigned gl_top = panda::msm_batch_next_group_log(batch, group_log_max);
+    for (unsigned gl = 1; gl <= gl_top; gl++)
+        if (!panda::msm_sort_tabled_batch_supported(log_n, gl, plan)) return hipErrorInvalidValue;
+    struct GroupGeom {
+        u64 stride;
+        unsigned K, chunks, long_cap;
+    };
+    auto group_geom = [&](unsigned gl) {
+        GroupGeom g;
+        g.stride = (u64)W << (log_n + gl);
+        g.K = acc_chunk_entries<Fq>(g.stride, 0u);
+        g.chunks = (unsigned)((g.stride + g.K - 1) / g.K);
+        g.long_cap = g.chunks / LONG_SPAN + 2;
+        return g;
+    };
+    // the reduction works per member: row / column split of a member's c - 1 bucket bits, as in msm_execute
+    const unsigned rc_b = (c - 1) / 2, rc_a = (c - 1) - rc_b;
+    const unsigned rc_rows = 1u << rc_a, rc_cols = 1u << rc_b, rc_csplit = rc_a > rc_b ? 2u : 1u;
+    const unsigned slots = 1 + rc_a + rc_b;
+    const unsigned rc_parts = std::max(1u, std::max(rc_rows, rc_cols * rc_csplit) / 512u);
+
+    // ---- scratch: maxima over the group sizes the batch may use (the chunk size steps with the group, so the pieces need not be monotonic)
+    const size_t G_top = (size_t)1 << gl_top;
+    size_t sz_sort = 0, sz_parts = 0, sz_llist = 0, sz_first = 0;
+    for (unsigned gl = 0; gl <= gl_top; gl++) {
+        const GroupGeom g = group_geom(gl);
+        sz_sort = std::max(sz_sort, gl ? panda::msm_sort_tabled_batch_bytes(log_n, gl, plan) : panda::msm_sort_tabled_bytes(log_n, plan));
+        sz_parts = std::max(sz_parts, panda::align256((size_t)g.chunks * 2 * PW * 4));
+        sz_llist = std::max(sz_llist, panda::align256((size_t)g.long_cap * 3 * 4));
+        sz_first = std::max(sz_first, panda::align256((size_t)g.chunks * 4));
+    }
+    const size_t sz_bacc = panda::align256(G_top * NB * PW * 4);
+    const size_t sz_l1 = panda::align256(G_top * (rc_rows + rc_cols * rc_csplit) * PW * 4);
+    const size_t sz_slots = panda::align256(G_top * slots * rc_parts * PW * 4);
+    const size_t sz_results = panda::align256((size_t)batch * 3 * LQ * 4);
+    panda::Arena &arena = panda::thread_arena();
+    PANDA_TRY(arena.reserve(sz_sort + sz_parts + sz_llist + sz_first + sz_bacc + sz_l1 + sz_slots + sz_results + 256 + 256 + 8192));
+    u32 *d_bacc = (u32 *)arena.take(sz_bacc);
+    u32 *d_parts = (u32 *)arena.take(sz_parts);
+    u32 *d_lcount = (u32 *)arena.take(256);
+    u32 *d_llist = (u32 *)arena.take(sz_llist);
+    u32 *d_first = (u32 *)arena.take(sz_first);
+    u32 *d_l1 = (u32 *)arena.take(sz_l1);
+    u32 *d_stale = (u32 *)arena.take(256);
+    u32 *d_slots = (u32 *)arena.take(sz_slots);
+    u32 *d_results = (u32 *)arena.take(sz_results); // wire-form results of the whole batch, when a kernel cannot address cfg.results
+    if (!d_bacc || !d_parts || !d_lcount || !d_llist || !d_first || !d_l1 || !d_stale || !d_slots || !d_results) return hipErrorOutOfMemory;
+    const size_t sort_mark = arena.used; // every group's sort carves its scratch from here again
+    u32 *mail = nullptr;
+    PANDA_TRY(panda::thread_mailbox(&mail)); // word 0: set by a digits kernel that finds the registered buffer changed
+    volatile u32 *h_flag = mail;
+    *h_flag = 0;
+    const panda::SampleCheck sample_check{(const u32 *)cfg.bases, reg->samples, n, 2u * LQ, d_stale, mail};
+    // results go straight to the caller's buffer where a kernel can address it (as in msm_execute), else through d_results and one copy
+    u32 *res_dev = nullptr;
+    {
+        hipPointerAttribute_t at{};
+        int dev = -1;
+        if (hipPointerGetAttributes(&at, cfg.results) == hipSuccess && hipGetDevice(&dev) == hipSuccess && at.devicePointer &&
+            ((at.type == hipMemoryTypeDevice && at.device == dev) || at.type == hipMemoryTypeHost))
+            res_dev = (u32 *)at.devicePointer;
+        else
+            (void)hipGetLastError();
+    }
+    u32 *res_out = res_dev ? res_dev : d_results;
+    const unsigned emit = cfg.msm_result_coordinate_type == PROJECTIVE ? 2u : 1u;
+    panda::thread_msm_clock() = panda::ClockDelta{};
+    struct LastGroupTimer { // only a call that asked for timing pays for the two events
+        hipEvent_t begin = nullptr, end = nullptr;
+        ~LastGroupTimer()
+        {
+            if (begin) (void)hipEventDestroy(begin);
+            if (end) (void)hipEventDestroy(end);
+        }
+    } timer;
+    if (timing) {
+        PANDA_TRY(hipEventCreate(&timer.begin));
+        PANDA_TRY(hipEventCreate(&timer.end));
+    }
+
+    const u32 *d_tables = (const u32 *)reg->converted;
+    for (unsigned done = 0; done < batch;) {
+        const unsigned gl = panda::msm_batch_next_group_log(batch - done, group_log_max), G = 1u << gl;
+        const bool last = done + G == batch;
+        const GroupGeom g = group_geom(gl);
+        const unsigned NBG = NB << gl; // the group's buckets as one list; read as [G][NB] by the reduction
+        const void *scalars_g = (const char *)cfg.scalars + (size_t)done * n * 32;
+        if (last && timing) PANDA_TRY(hipEventRecord(timer.begin, stream));
+        arena.used = sort_mark;
+        panda::SortResult sorted{};
+        if (gl)
+            PANDA_TRY(panda::msm_sort_tabled_batch(stream, arena, fr, scalars_g, log_n, gl, plan, &sorted, sample_check));
+        else // a group of one member is the ordinary tabled sort
+            PANDA_TRY(panda::msm_sort_tabled(stream, arena, fr, scalars_g, log_n, plan, panda::SortEvents{nullptr, nullptr}, &sorted, panda::SortPlacement{0, 0}, sample_check));
+        if (sorted.lists != 1 || sorted.NB != NBG || sorted.stride != g.stride) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_chunk_first, dim3((NBG + 255) / 256, 1), dim3(256), 0, stream, sorted.off, d_first, NBG, g.K, g.chunks);
+        const dim3 acc_grid((g.chunks + 127) / 128, 1);
+        const AccPart whole{nullptr, 0u, 0u, 1u, NBG, nullptr};
+        // the built-in k_accumulate of the curve (msm_execute): the sorted words through LDS for the 9-limb prime fields, the plain kernel otherwise
+        if constexpr (!AccSingleShape<Fq>::value && !IsExt2<Fq>::value && Fq::N <= 9) {
+            if (g.K % 16 == 0)
+                hipLaunchKernelGGL((k_accumulate<Fq, false, 4, false, true>), acc_grid, dim3(128), 0, stream, d_tables, sorted.sorted, sorted.off, d_bacc, d_parts, g.stride, NBG, g.K,
+                                   g.chunks, d_lcount, d_stale, whole, (const u32 *)d_first);
+            else
+                hipLaunchKernelGGL((k_accumulate<Fq, false>), acc_grid, dim3(128), 0, stream, d_tables, sorted.sorted, sorted.off, d_bacc, d_parts, g.stride, NBG, g.K, g.chunks,
+                                   d_lcount, d_stale, whole, (const u32 *)d_first);
+        } else
+            hipLaunchKernelGGL((k_accumulate<Fq, false>), acc_grid, dim3(128), 0, stream, d_tables, sorted.sorted, sorted.off, d_bacc, d_parts, g.stride, NBG, g.K, g.chunks,
+                               d_lcount, d_stale, whole, (const u32 *)d_first);
+        hipLaunchKernelGGL((k_fixup<Fq, false>), dim3((NBG + 255) / 256, 1), dim3(256), 0, stream, sorted.off, d_parts, d_bacc, d_bacc, NBG, g.K, g.chunks, d_lcount, d_llist,
+                           g.long_cap);
+        hipLaunchKernelGGL(k_fixup_long<Fq>, dim3(LONG_BLOCKS, 1), dim3(256), 0, stream, d_parts, d_bacc, 0u, NBG, g.chunks, d_lcount, d_llist, g.long_cap);
+        // one list per member from here on
+        u32 *d_rows = d_l1, *d_cols = d_l1 + (size_t)G * rc_rows * PW;
+        hipLaunchKernelGGL(k_sum_lines<Fq>, dim3(rc_rows + rc_cols * rc_csplit, G), dim3(64), 0, stream, d_bacc, d_rows, d_cols, rc_rows, rc_cols, rc_csplit);
+        hipLaunchKernelGGL(k_weighted_slots<Fq>, dim3(slots, G, rc_parts), dim3(64), 0, stream, d_rows, d_cols, d_slots, rc_a, rc_b, rc_csplit);
+        hipLaunchKernelGGL(k_slot_total<Fq>, dim3(G), dim3(64), 0, stream, d_slots, res_out + (size_t)done * 3 * LQ, slots * rc_parts, emit);
+        if (last && timing) PANDA_TRY(hipEventRecord(timer.end, stream));
+        PANDA_TRY(hipGetLastError());
+        done += G;
+    }
+    if (!res_dev) PANDA_TRY(hipMemcpyAsync(cfg.results, d_results, (size_t)batch * 3 * LQ * 4, hipMemcpyDefault, stream)); // behind the last kernel
+    PANDA_TRY(hipStreamSynchronize(stream));
+    for (int i = 0; i < 8; i++) phase_ms[i] = 0;
+    if (*h_flag != 0) { // the caller's buffer is not what was registered: nothing written means anything
+        if (stale) *stale = true;
+        return hipSuccess;
+    }
+    float ms = 0;
+    if (timing && hipEventElapsedTime(&ms, timer.begin, timer.end) == hipSuccess) phase_ms[7] = ms;
     return hipSuccess;
 }
 

@@ -86,4 +86,15 @@ size_t msm_sort_tabled_bytes(unsigned log_n, const WindowPlan &plan);
 hipError_t msm_sort_tabled(hipStream_t stream, Arena &arena, unsigned fr, const void *scalars, unsigned log_n, const WindowPlan &plan, SortEvents ev,
                            SortResult *out, SortPlacement place = SortPlacement{0, 0}, SampleCheck check = SampleCheck{}, SortSplit *split = nullptr);
 
+// Batched tabled mode: 2^group_log scalar vectors ("members") of 2^log_n scalars each, contiguous in `scalars`, against ONE set of
+// tables.  The group is sorted as one list of 2^(log_n + group_log) scalars whose bucket id carries the member index above the widest
+// window's c - 1 bits -- out->NB = 2^(c - 1 + group_log) buckets, member j's being [j 2^(c-1), (j + 1) 2^(c-1)) -- and whose entries
+// name row (k << log_n) + (i mod 2^log_n): every member gathers from the same tables.  out->lists = 1, out->stride = W 2^(log_n + group_log).
+// check.n stays the number of rows of the base buffer.  One stream, no point ranges, no split; the level-3 merge policy is the plan's own
+// (msm_sort_set_wide_merge does not apply).
+bool msm_sort_tabled_batch_supported(unsigned log_n, unsigned group_log, const WindowPlan &plan);
+size_t msm_sort_tabled_batch_bytes(unsigned log_n, unsigned group_log, const WindowPlan &plan);
+hipError_t msm_sort_tabled_batch(hipStream_t stream, Arena &arena, unsigned fr, const void *scalars, unsigned log_n, unsigned group_log, const WindowPlan &plan,
+                                 SortResult *out, SampleCheck check);
+
 } // namespace panda

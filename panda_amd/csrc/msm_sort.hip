@@ -72,11 +72,18 @@ __device__ __forceinline__ void check_samples(const panda::SampleCheck &sc)
     }
 }
 
+// A batch of scalar vectors against one set of tables (msm_sort_tabled_batch): scalar i belongs to member i >> log_n, and the member
+// index sits above the widest window's magnitude bits in every code, so that each member sorts into a bucket space of its own.
+struct DigitsBatch {
+    unsigned log_n, prefix_bit; // scalars per member (log2); c - 1 of the widest window
+};
+
 // scalar (Montgomery wire form) -> W signed digits.  code = (neg << SIGN) | (|d| - 1), ZERO for d = 0.
 // Replaces init_handle_scalars_kernel + the slice extraction of calc_lens/fill_arrs (msm_cuda.cuh:148-205,232-282);
-// the scalars are only read.
-template <class Fr, class Code>
-__global__ void __launch_bounds__(256) k_digits(const u32 *__restrict__ scalars, Code *__restrict__ dig, u64 n, panda::WindowPlan plan, panda::SampleCheck sc)
+// the scalars are only read.  BATCH: code = (neg << SIGN) | (member << prefix_bit) | (|d| - 1).
+template <class Fr, class Code, bool BATCH = false>
+__global__ void __launch_bounds__(256) k_digits(const u32 *__restrict__ scalars, Code *__restrict__ dig, u64 n, panda::WindowPlan plan, panda::SampleCheck sc,
+                                                DigitsBatch bg)
 {
     typedef CodeTraits<Code> CT;
     constexpr int L = Fr::L;
@@ -88,6 +95,7 @@ __global__ void __launch_bounds__(256) k_digits(const u32 *__restrict__ scalars,
     fe_wire_to_canonical<Fr>(s, w);
     s[L] = 0;
     u32 carry = 0;
+    const u32 prefix = BATCH ? (u32)(i >> bg.log_n) << bg.prefix_bit : 0u;
     for (unsigned k = 0; k < plan.W; k++) {
         const unsigned c = plan.width[k];
         const u32 half = 1u << (c - 1), full = 1u << c, mask = full - 1;
@@ -102,10 +110,10 @@ __global__ void __launch_bounds__(256) k_digits(const u32 *__restrict__ scalars,
         if (raw >= half) { // negative digit raw - 2^c (or zero when raw == 2^c)
             u32 mag = full - raw;
             carry = 1;
-            code = mag ? ((1u << CT::SIGN) | (mag - 1)) : CT::ZERO;
+            code = mag ? ((1u << CT::SIGN) | prefix | (mag - 1)) : CT::ZERO;
         } else {
             carry = 0;
-            code = raw ? (raw - 1) : CT::ZERO;
+            code = raw ? (prefix | (raw - 1)) : CT::ZERO;
         }
         dig[(u64)k * n + i] = (Code)code;
     }
@@ -118,9 +126,9 @@ struct DigitsHistGeom {
     unsigned lo_bits, H, tiles;
 };
 
-template <class Fr, class Code>
+template <class Fr, class Code, bool BATCH = false>
 __global__ void __launch_bounds__(1024) k_digits_hist(const u32 *__restrict__ scalars, Code *__restrict__ dig, u32 *__restrict__ tile_hist, u64 n,
-                                                     panda::WindowPlan plan, DigitsHistGeom g, panda::SampleCheck sc)
+                                                     panda::WindowPlan plan, DigitsHistGeom g, panda::SampleCheck sc, DigitsBatch bg)
 {
     typedef CodeTraits<Code> CT;
     constexpr int L = Fr::L;
@@ -137,6 +145,7 @@ __global__ void __launch_bounds__(1024) k_digits_hist(const u32 *__restrict__ sc
         fe_wire_to_canonical<Fr>(s, w);
         s[L] = 0;
         u32 carry = 0;
+        const u32 prefix = BATCH ? (u32)(i >> bg.log_n) << bg.prefix_bit : 0u;
         for (unsigned k = 0; k < plan.W; k++) {
             const unsigned c = plan.width[k];
             const u32 half = 1u << (c - 1), full = 1u << c, mask = full - 1;
@@ -151,10 +160,10 @@ __global__ void __launch_bounds__(1024) k_digits_hist(const u32 *__restrict__ sc
             if (raw >= half) {
                 u32 mag = full - raw;
                 carry = 1;
-                code = mag ? ((1u << CT::SIGN) | (mag - 1)) : CT::ZERO;
+                code = mag ? ((1u << CT::SIGN) | prefix | (mag - 1)) : CT::ZERO;
             } else {
                 carry = 0;
-                code = raw ? (raw - 1) : CT::ZERO;
+                code = raw ? (prefix | (raw - 1)) : CT::ZERO;
             }
             dig[(u64)k * n + i] = (Code)code;
             if (code != CT::ZERO) atomicAdd(&hist[k * g.H + ((code & CT::MAG) >> g.lo_bits)], 1u);
@@ -481,6 +490,7 @@ struct TabledGeom {
     u32 row0;            // and the first row of the point range being sorted (both = log_n, 0 unless a call runs in point-range chunks)
     unsigned per_window; // 0: one list, level 3 merges the W windows of a cell (tabled mode);  1: W lists, a level-3 cell is one window's
                          // (plain mode with windows too wide for the two-level sort): cells are numbered window-major, entries name row0 + i
+    u32 row_mask;        // batch (k3_merge<.., BATCH>): entries name row (k << row_shift) + (i & row_mask) -- scalar i of ANY member names row i mod n
 };
 __host__ __device__ __forceinline__ unsigned seg_of(const TabledGeom &g, unsigned k, unsigned h1) { return h1 * g.W + k; }
 
@@ -785,7 +795,8 @@ __device__ unsigned long long g_k3_stamps[1024 * 8];
 // PER = K3_PER_WIDE: a cell of up to 2 K3_CAP entries is still read once -- 32 words and their ranks in registers (one workgroup per CU
 // instead of two) -- and leaves through the same LDS image in two rounds.  For the cells of the lower half of the bucket space at 2^25 and
 // 2^26 points, where the entry word leaves b3 only 5 or 6 bits and a smaller cell would make level 1 a 512-way partition.
-template <unsigned PER, unsigned THREADS = K3_THREADS>
+// BATCH (msm_sort_tabled_batch): the point id of an entry is its scalar's index in the whole group; the row it names is that index mod n.
+template <unsigned PER, unsigned THREADS = K3_THREADS, bool BATCH = false>
 __global__ void __launch_bounds__(THREADS) k3_merge(const u32 *__restrict__ p2, const u32 *__restrict__ part_off, const u32 *__restrict__ sub_off,
                                               const u32 *__restrict__ cell_off, u32 *__restrict__ off, u32 *__restrict__ sorted, TabledGeom g, unsigned NB, SortRange R)
 {
@@ -841,7 +852,8 @@ __global__ void __launch_bounds__(THREADS) k3_merge(const u32 *__restrict__ p2, 
     // final word: row k*n + i of the tables (tabled mode) or row i of the bases (per-window mode), bit 31 = negate
     const unsigned table_shift = g.per_window ? 32u : g.row_shift;
     auto final_word = [&](u32 v, unsigned k) -> u32 {
-        return ((v & id_mask) + g.row0 + (table_shift < 32 ? (k << table_shift) : 0u)) | (((v >> g.log_n) & 1u) << 31);
+        const u32 id = BATCH ? v & id_mask & g.row_mask : v & id_mask;
+        return (id + g.row0 + (table_shift < 32 ? (k << table_shift) : 0u)) | (((v >> g.log_n) & 1u) << 31);
     };
 
     if (closes_part && tid == 0) ow[(u64)(q + 1) << g.b3] = out_rel + N;
@@ -1041,10 +1053,10 @@ SortGeom plain_geom(unsigned log_n, unsigned c)
     return g;
 }
 
-TabledGeom tabled_geom(unsigned log_n, const panda::WindowPlan &plan, bool per_window = false)
+// B: bits of the bucket id -- the widest window's c - 1, plus the member bits of a batch (log_n then counts the whole group's scalars)
+TabledGeom tabled_geom(unsigned log_n, const panda::WindowPlan &plan, unsigned B, bool per_window = false)
 {
     TabledGeom g{};
-    const unsigned B = plan.width[0] - 1;
     g.log_n = log_n;
     g.W = plan.W;
     g.per_window = per_window ? 1u : 0u;
@@ -1069,30 +1081,39 @@ TabledGeom tabled_geom(unsigned log_n, const panda::WindowPlan &plan, bool per_w
     g.max_tiles2 = (unsigned)(E / SORT_TILE + g.S + 1);
     g.row_shift = log_n;
     g.row0 = 0;
+    g.row_mask = ~0u;
     return g;
 }
 
 
+// batch != nullptr (u32 codes only): the member index goes into every code
 template <class Fr, class Code>
-void launch_digits(hipStream_t stream, const void *scalars, Code *dig, u64 n, const panda::WindowPlan &plan, const panda::SampleCheck &sc)
+void launch_digits(hipStream_t stream, const void *scalars, Code *dig, u64 n, const panda::WindowPlan &plan, const panda::SampleCheck &sc, const DigitsBatch *batch)
 {
-    hipLaunchKernelGGL((k_digits<Fr, Code>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const u32 *)scalars, dig, n, plan, sc);
+    if constexpr (sizeof(Code) == 4) {
+        if (batch) {
+            hipLaunchKernelGGL((k_digits<Fr, Code, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const u32 *)scalars, dig, n, plan, sc, *batch);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_digits<Fr, Code>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const u32 *)scalars, dig, n, plan, sc, DigitsBatch{});
 }
 
 template <class Code>
-void launch_digits_for(unsigned fr, hipStream_t stream, const void *scalars, Code *dig, u64 n, const panda::WindowPlan &plan, const panda::SampleCheck &sc)
+void launch_digits_for(unsigned fr, hipStream_t stream, const void *scalars, Code *dig, u64 n, const panda::WindowPlan &plan, const panda::SampleCheck &sc,
+                       const DigitsBatch *batch = nullptr)
 {
     switch (fr) {
-    case 0: launch_digits<Bn254Fr, Code>(stream, scalars, dig, n, plan, sc); break;
-    case 1: launch_digits<Bls377Fr, Code>(stream, scalars, dig, n, plan, sc); break;
-    default: launch_digits<Bls381Fr, Code>(stream, scalars, dig, n, plan, sc); break;
+    case 0: launch_digits<Bn254Fr, Code>(stream, scalars, dig, n, plan, sc, batch); break;
+    case 1: launch_digits<Bls377Fr, Code>(stream, scalars, dig, n, plan, sc, batch); break;
+    default: launch_digits<Bls381Fr, Code>(stream, scalars, dig, n, plan, sc, batch); break;
     }
 }
 
 // digits + level-1 histogram; returns false if the fused kernel does not apply (the caller then runs k_digits + k_part_hist)
 template <class Fr, class Code>
 bool launch_digits_hist(hipStream_t stream, const void *scalars, Code *dig, u32 *tile_hist, u64 n, const panda::WindowPlan &plan, const SortGeom &g,
-                        const panda::SampleCheck &sc)
+                        const panda::SampleCheck &sc, const DigitsBatch *batch)
 {
     const size_t lds = (size_t)plan.W * g.H * 4;
     if (g.tiles < 512 || lds > 48 * 1024) return false;
@@ -1100,18 +1121,24 @@ bool launch_digits_hist(hipStream_t stream, const void *scalars, Code *dig, u32 
     // a thread walks its scalars one after the other (load, convert, W stores): with 256 threads per tile a 2^22-point call ran two waves
     // per SIMD and the kernel was bound by those round trips (0.23 ms for 0.35 GB); 1024 threads until the tiles alone fill the chip
     const unsigned threads = g.tiles >= 8192 ? 512u : 1024u;
-    hipLaunchKernelGGL((k_digits_hist<Fr, Code>), dim3(g.tiles), dim3(threads), lds, stream, (const u32 *)scalars, dig, tile_hist, n, plan, dg, sc);
+    if constexpr (sizeof(Code) == 4) {
+        if (batch) {
+            hipLaunchKernelGGL((k_digits_hist<Fr, Code, true>), dim3(g.tiles), dim3(threads), lds, stream, (const u32 *)scalars, dig, tile_hist, n, plan, dg, sc, *batch);
+            return true;
+        }
+    }
+    hipLaunchKernelGGL((k_digits_hist<Fr, Code>), dim3(g.tiles), dim3(threads), lds, stream, (const u32 *)scalars, dig, tile_hist, n, plan, dg, sc, DigitsBatch{});
     return true;
 }
 
 template <class Code>
 bool launch_digits_hist_for(unsigned fr, hipStream_t stream, const void *scalars, Code *dig, u32 *tile_hist, u64 n, const panda::WindowPlan &plan,
-                            const SortGeom &g, const panda::SampleCheck &sc)
+                            const SortGeom &g, const panda::SampleCheck &sc, const DigitsBatch *batch = nullptr)
 {
     switch (fr) {
-    case 0: return launch_digits_hist<Bn254Fr, Code>(stream, scalars, dig, tile_hist, n, plan, g, sc);
-    case 1: return launch_digits_hist<Bls377Fr, Code>(stream, scalars, dig, tile_hist, n, plan, g, sc);
-    default: return launch_digits_hist<Bls381Fr, Code>(stream, scalars, dig, tile_hist, n, plan, g, sc);
+    case 0: return launch_digits_hist<Bn254Fr, Code>(stream, scalars, dig, tile_hist, n, plan, g, sc, batch);
+    case 1: return launch_digits_hist<Bls377Fr, Code>(stream, scalars, dig, tile_hist, n, plan, g, sc, batch);
+    default: return launch_digits_hist<Bls381Fr, Code>(stream, scalars, dig, tile_hist, n, plan, g, sc, batch);
     }
 }
 
@@ -1154,10 +1181,12 @@ static WindowPlan safe_plan(unsigned c)
 
 WindowPlan make_safe_window_plan(unsigned fr, unsigned c) { return fr == 0 ? safe_plan<Bn254Fr>(c) : (fr == 1 ? safe_plan<Bls377Fr>(c) : safe_plan<Bls381Fr>(c)); }
 
-static bool sort3_supported(unsigned log_n, const WindowPlan &plan, bool per_window);
-static size_t sort3_bytes(unsigned log_n, const WindowPlan &plan, bool per_window);
+// group_log > 0 (tabled mode only): a batch of 2^group_log scalar vectors over one set of tables; log_n counts the scalars of the whole
+// group, the bucket id carries the member index above the widest window's c - 1 bits
+static bool sort3_supported(unsigned log_n, const WindowPlan &plan, bool per_window, unsigned group_log = 0);
+static size_t sort3_bytes(unsigned log_n, const WindowPlan &plan, bool per_window, unsigned group_log = 0);
 static hipError_t sort3(hipStream_t stream, Arena &arena, unsigned fr, const void *scalars, unsigned log_n, const WindowPlan &plan, SortEvents ev, SortResult *out,
-                        SortPlacement place, SampleCheck check, bool per_window, SortSplit *split = nullptr);
+                        SortPlacement place, SampleCheck check, bool per_window, SortSplit *split = nullptr, unsigned group_log = 0);
 
 bool msm_sort_plain_supported(unsigned log_n, const WindowPlan &plan)
 {
@@ -1218,22 +1247,23 @@ hipError_t msm_sort_plain(hipStream_t stream, Arena &arena, unsigned fr, const v
     return hipGetLastError();
 }
 
-static bool sort3_supported(unsigned log_n, const WindowPlan &plan, bool per_window)
+static bool sort3_supported(unsigned log_n, const WindowPlan &plan, bool per_window, unsigned group_log)
 {
     const unsigned c = plan.width[0];
     if (plan.W > 32 || plan.W < 1 || c < 4 || c > 24 || log_n > 26 || log_n < 1) return false;
+    if (group_log && (per_window || group_log >= log_n)) return false;
     unsigned wbits = 0;
     while ((1u << wbits) < plan.W) wbits++;
     if (log_n + wbits > 31) return false;
-    const TabledGeom g = tabled_geom(log_n, plan, per_window);
+    const TabledGeom g = tabled_geom(log_n, plan, c - 1 + group_log, per_window);
     return g.b1 <= 10 && g.b2 <= 8 && g.b3 <= 7 && g.S <= 16384 && g.b3 + 1 + log_n <= 32;
 }
 
-static size_t sort3_bytes(unsigned log_n, const WindowPlan &plan, bool per_window)
+static size_t sort3_bytes(unsigned log_n, const WindowPlan &plan, bool per_window, unsigned group_log)
 {
     const u64 E = (u64)plan.W << log_n;
-    const unsigned NB = 1u << (plan.width[0] - 1);
-    const TabledGeom g = tabled_geom(log_n, plan, per_window);
+    const unsigned NB = 1u << (plan.width[0] - 1 + group_log);
+    const TabledGeom g = tabled_geom(log_n, plan, plan.width[0] - 1 + group_log, per_window);
     const unsigned tiles1 = (unsigned)((((u64)1 << log_n) + SORT_TILE - 1) / SORT_TILE);
     const size_t cells = (size_t)g.Q * (per_window ? g.W : 1u), lists = per_window ? g.W : 1u;
     return align256(E * 4 + 16) + 2 * align256((size_t)g.W * tiles1 * g.H1 * 4) + 2 * align256((size_t)g.W * (g.H1 + 1) * 4) + align256(E * 4 + 64) + align256(E + 16) +
@@ -1246,13 +1276,20 @@ static std::atomic<unsigned> g_wide_merge{0};
 
 // the three-level sort: tabled mode (one list over all windows) or per-window mode (W lists)
 static hipError_t sort3(hipStream_t stream, Arena &arena, unsigned fr, const void *scalars, unsigned log_n, const WindowPlan &plan, SortEvents ev, SortResult *out,
-                        SortPlacement place, SampleCheck check, bool per_window, SortSplit *split)
+                        SortPlacement place, SampleCheck check, bool per_window, SortSplit *split, unsigned group_log)
 {
-    if (!sort3_supported(log_n, plan, per_window)) return hipErrorInvalidValue;
+    if (!sort3_supported(log_n, plan, per_window, group_log)) return hipErrorInvalidValue;
+    if (group_log && (place.row_shift || split)) return hipErrorInvalidValue; // a batch runs whole members, on one stream
     const u64 n = (u64)1 << log_n;
     const u64 E = (u64)plan.W << log_n;
-    const unsigned W = plan.W, NB = 1u << (plan.width[0] - 1);
-    TabledGeom g = tabled_geom(log_n, plan, per_window);
+    const unsigned W = plan.W, NB = 1u << (plan.width[0] - 1 + group_log);
+    TabledGeom g = tabled_geom(log_n, plan, plan.width[0] - 1 + group_log, per_window);
+    const DigitsBatch batch{log_n - group_log, plan.width[0] - 1u};
+    const DigitsBatch *batch_p = group_log ? &batch : nullptr;
+    if (group_log) { // scalar i of the group is scalar i mod 2^(log_n - group_log) of its member: row i mod n of every table
+        g.row_shift = log_n - group_log;
+        g.row_mask = (1u << (log_n - group_log)) - 1;
+    }
     if (place.row_shift) { // a point range [row0, row0 + n) of tables that hold 2^row_shift rows each (per-window mode: of the base array)
         if (place.row_shift < log_n || place.row_shift > 26) return hipErrorInvalidValue;
         const u64 last_row = (per_window ? 0 : ((u64)(W - 1) << place.row_shift)) + place.row0 + n;
@@ -1291,8 +1328,8 @@ static hipError_t sort3(hipStream_t stream, Arena &arena, unsigned fr, const voi
         !d_off || !d_sorted)
         return hipErrorOutOfMemory;
 
-    const bool fused = launch_digits_hist_for<u32>(fr, stream, scalars, d_dig, d_thist1, n, plan, g1, check);
-    if (!fused) launch_digits_for<u32>(fr, stream, scalars, d_dig, n, plan, check);
+    const bool fused = launch_digits_hist_for<u32>(fr, stream, scalars, d_dig, d_thist1, n, plan, g1, check, batch_p);
+    if (!fused) launch_digits_for<u32>(fr, stream, scalars, d_dig, n, plan, check, batch_p);
     if (ev.digits_done) PANDA_TRY(hipEventRecord(ev.digits_done, stream));
     // level 1, per window
     if (!fused) hipLaunchKernelGGL(k_part_hist<u32>, dim3(g1.tiles, W), dim3(256), 0, stream, d_dig, d_thist1, g1);
@@ -1319,6 +1356,7 @@ static hipError_t sort3(hipStream_t stream, Arena &arena, unsigned fr, const voi
     // cells of the lower half of the bucket space, which every window reaches
     unsigned wide_cells = 0, small_from = ~0u; // cells [small_from, Q): few enough entries for 256-thread workgroups
     if (!per_window) {
+        const u64 n = (u64)1 << (log_n - group_log); // scalars per bucket space: a member's
         double per_bucket = 0;
         unsigned narrow = plan.width[0];
         for (unsigned k = 0; k < plan.W; k++) {
@@ -1332,10 +1370,15 @@ static hipError_t sort3(hipStream_t stream, Arena &arena, unsigned fr, const voi
         for (unsigned k = 0; k < plan.W; k++)
             if (plan.width[k] == plan.width[0]) sparse_bucket += ldexp((double)n, -(int)(plan.width[k] - 1));
         if (narrow + 1 == plan.width[0] && ldexp(sparse_bucket, (int)g.b3) <= 256.0 * K3_PER * 0.85) small_from = g.Q / 2;
+        const bool plan_wide = wide_cells != 0;
         const unsigned mode = g_wide_merge.load(std::memory_order_relaxed); // tests: every cell through the wide variant, or none
         if (mode == 1) wide_cells = g.Q, small_from = ~0u;
         if (mode == 2) wide_cells = 0, small_from = ~0u;
         if (mode == 3) wide_cells = 0, small_from = 0; // every cell through the 256-thread variant
+        // a batch repeats the dense and the sparse half in every member's part of the bucket space: where a single call would merge its
+        // dense half with the wide variant, every cell of the batch takes it (a sparse cell loses a little occupancy and nothing else);
+        // otherwise every cell takes the ordinary one.  The experiment modes above do not apply.
+        if (group_log) wide_cells = plan_wide ? g.Q : 0u, small_from = ~0u;
     }
     auto level3_merge = [&](hipStream_t s, const SortRange &R) {
         hipLaunchKernelGGL(k3_cell_offsets, dim3((R.q_hi - R.q_lo + 1023) / 1024), dim3(s == stream ? 1024 : 256), 0, s, d_cellcnt, d_blksum, d_celloff, g, R);
@@ -1344,12 +1387,18 @@ static hipError_t sort3(hipStream_t stream, Arena &arena, unsigned fr, const voi
             const unsigned wide_hi = std::min(std::max(wide_cells, R.q_lo), R.q_hi);
             if (wide_hi > R.q_lo) {
                 const SortRange Rw{R.s_lo, R.s_hi, R.q_lo, wide_hi};
-                hipLaunchKernelGGL(k3_merge<K3_PER_WIDE>, dim3(wide_hi - R.q_lo), dim3(K3_THREADS), 0, s, d_p2, d_poff, d_suboff, d_celloff, d_off, d_sorted, g, NB, Rw);
+                if (group_log)
+                    hipLaunchKernelGGL((k3_merge<K3_PER_WIDE, K3_THREADS, true>), dim3(wide_hi - R.q_lo), dim3(K3_THREADS), 0, s, d_p2, d_poff, d_suboff, d_celloff, d_off, d_sorted, g, NB, Rw);
+                else
+                    hipLaunchKernelGGL(k3_merge<K3_PER_WIDE>, dim3(wide_hi - R.q_lo), dim3(K3_THREADS), 0, s, d_p2, d_poff, d_suboff, d_celloff, d_off, d_sorted, g, NB, Rw);
             }
             const unsigned small_lo = std::min(std::max(small_from, wide_hi), R.q_hi);
             if (small_lo > wide_hi) {
                 const SortRange Rn{R.s_lo, R.s_hi, wide_hi, small_lo};
-                hipLaunchKernelGGL(k3_merge<K3_PER>, dim3(small_lo - wide_hi), dim3(K3_THREADS), 0, s, d_p2, d_poff, d_suboff, d_celloff, d_off, d_sorted, g, NB, Rn);
+                if (group_log)
+                    hipLaunchKernelGGL((k3_merge<K3_PER, K3_THREADS, true>), dim3(small_lo - wide_hi), dim3(K3_THREADS), 0, s, d_p2, d_poff, d_suboff, d_celloff, d_off, d_sorted, g, NB, Rn);
+                else
+                    hipLaunchKernelGGL(k3_merge<K3_PER>, dim3(small_lo - wide_hi), dim3(K3_THREADS), 0, s, d_p2, d_poff, d_suboff, d_celloff, d_off, d_sorted, g, NB, Rn);
             }
             if (R.q_hi > small_lo) {
                 const SortRange Rs{R.s_lo, R.s_hi, small_lo, R.q_hi};
@@ -1408,6 +1457,18 @@ extern "C" int panda_debug_k3_stamps(unsigned long long *out) { return (int)hipM
 void msm_sort_set_wide_merge(unsigned mode) { g_wide_merge.store(mode, std::memory_order_relaxed); }
 bool msm_sort_tabled_supported(unsigned log_n, const WindowPlan &plan) { return sort3_supported(log_n, plan, false); }
 size_t msm_sort_tabled_bytes(unsigned log_n, const WindowPlan &plan) { return sort3_bytes(log_n, plan, false); }
+
+bool msm_sort_tabled_batch_supported(unsigned log_n, unsigned group_log, const WindowPlan &plan)
+{
+    return group_log >= 1 && log_n >= 1 && log_n + group_log <= 26 && sort3_supported(log_n + group_log, plan, false, group_log);
+}
+size_t msm_sort_tabled_batch_bytes(unsigned log_n, unsigned group_log, const WindowPlan &plan) { return sort3_bytes(log_n + group_log, plan, false, group_log); }
+hipError_t msm_sort_tabled_batch(hipStream_t stream, Arena &arena, unsigned fr, const void *scalars, unsigned log_n, unsigned group_log, const WindowPlan &plan,
+                                 SortResult *out, SampleCheck check)
+{
+    if (!msm_sort_tabled_batch_supported(log_n, group_log, plan)) return hipErrorInvalidValue;
+    return sort3(stream, arena, fr, scalars, log_n + group_log, plan, SortEvents{nullptr, nullptr}, out, SortPlacement{0, 0}, check, false, nullptr, group_log);
+}
 
 hipError_t msm_sort_tabled(hipStream_t stream, Arena &arena, unsigned fr, const void *scalars, unsigned log_n, const WindowPlan &plan, SortEvents ev,
                            SortResult *out, SortPlacement place, SampleCheck check, SortSplit *split)

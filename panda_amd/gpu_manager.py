@@ -373,6 +373,38 @@ def panda_msm_bn254_gpu_with_cached_bases_batched(gm: PandaGpuManager, scalars_b
     return results
 
 
+def panda_msm_gpu_batch_with_cached_bases(gm: PandaGpuManager, scalars_batches, bases_index: int, curve: int = BN254) -> list:
+    """Additive: a run of MSMs over one cached base set in ONE library call (panda_msm_execute_batch).  The vectors are uploaded into one
+    device buffer, member after member; against precomputed tables (precompute_cached_bases) the library fuses groups of members into one
+    sort + accumulate each, otherwise it runs them one after the other.  Returns the results in order; each is the same group element
+    as panda_msm_bn254_gpu_with_cached_bases on that vector."""
+    batches = [_as_bytes(b) for b in scalars_batches]
+    if not batches:
+        return []
+    d_bases = gm.get_params_bases_ptr_mut(bases_index)
+    if d_bases is None:
+        raise PandaGpuError("BasesIndexErr")
+    size = batches[0].size
+    if any(b.size != size for b in batches):
+        raise PandaGpuError("SchedulingErr")
+    log_n = log_2(size // FIELD_ELEMENT_LEN)
+    lib = ffi.load()
+    nres = _RESULT_BYTES[curve]
+    dev = C.c_void_p()
+    out = np.zeros(len(batches) * nres, dtype=np.uint8)  # pageable host memory: the library copies the results out itself
+    try:
+        ffi.check(lib.panda_malloc(C.byref(dev), len(batches) * size), "AsyncPoolMallocErr")
+        for k, b in enumerate(batches):
+            ffi.check(lib.panda_memcpy_async(C.c_void_p(dev.value + k * size), _ptr(b), size, gm.h2d_stream.raw), "AsyncMemcopyErr")
+        gm.wait_h2d()
+        cfg = ffi.MSMConfiguration(gm.mem_pool, gm.exec_stream.raw, d_bases, dev.value, _ptr(out), log_n, gm.msm_result_coordinate_type)
+        ffi.check(lib.panda_msm_execute_batch(curve, cfg, len(batches)), "SchedulingErr")
+    finally:
+        if dev:
+            lib.panda_free(dev)
+    return [out[k * nres:(k + 1) * nres].copy() for k in range(len(batches))]
+
+
 def panda_msm_bn254_gpu_with_cached_scalars(gm: PandaGpuManager, scalars_index: int, bases, curve: int = BN254) -> np.ndarray:
     """unit.rs:190-275: n comes from the bases length (len / 64, unit.rs:203)."""
     b = _as_bytes(bases)
