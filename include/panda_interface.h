@@ -300,6 +300,37 @@ panda_error panda_ntt_pass_plan(unsigned log_n, unsigned *passes, unsigned *radi
 panda_error panda_ntt_set_streamed_tables(unsigned mode);
 /* whole-transform twiddle-table sets built so far by the calling host thread: a repeated transform must not add to it (cache hit) */
 panda_error panda_ntt_table_builds(uint64_t *count);
+/* `batch` transforms of 2^log_n points over one field with one root in ONE call: every pass is launched once over all members, with one
+ * table set and one synchronisation -- the shape a prover's round transforms its polynomials in.
+ *   field: 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr.  kind: which single call a member runs as (below).
+ *   exec_cfg is the single call's struct.  d_src and d_dst are device buffers of batch x 2^log_n x 32 bytes, member j at byte offset
+ *     j x 2^log_n x 32 of either; d_omega is the HOST pointer to the FORWARD root for every kind; `shift` the HOST pointer to the coset
+ *     generator (32 bytes, Montgomery form, non-zero) for the coset kinds, ignored otherwise (may be NULL).
+ *   *flag is what the single call of that kind and size writes (passes & 1 of the plan that kind runs): all members' results are in d_src
+ *     (0) or in d_dst (1), member after member; the other buffer is scratch.  Member j's output is byte for byte what the single call of
+ *     that kind writes for member j alone.  Synchronous on return.  Bytes outside the `batch` members are never written.
+ *   Members of fewer than 2^10 points share a workgroup (1024 >> log_n whole members each, fewer in the last one); from 2^11 points on
+ *     the grid of every pass kernel covers batch x tiles-per-member tiles.  The coset kinds apply the shift as one sweep over the whole
+ *     batch in front of (forward) or behind (inverse) the passes.  log_n == 0 transforms nothing (flag 0).
+ *   The twiddle tables are the calling thread's whole-transform cache under the single call's key: a batch after a single call of the
+ *     same field, size, kind and root builds nothing, and the other way round; the streamed-table policy applies per member size (one
+ *     table as large as ONE member serves all).  panda_ntt_last_device_ms / panda_ntt_last_clock report the batch's passes.
+ *   panda_error_invalid_value, nothing launched: field > 2, kind > 5, batch == 0 or > PANDA_NTT_MAX_BATCH, log_n > 28, batch x 2^log_n >
+ *     2^28 elements, NULL d_src / d_dst / d_omega / flag, NULL or zero shift for a coset kind (all checked before any runtime call), and
+ *     d_src / d_dst of this library's allocators shorter than `batch` members. */
+#define PANDA_NTT_MAX_BATCH 4096
+#define PANDA_NTT_FORWARD 0u            /* panda_ntt_execute_<field>_v1 */
+#define PANDA_NTT_INVERSE 1u            /* ..._inverse (n^-1 fused) */
+#define PANDA_NTT_BITREV_OUT 2u         /* ..._bitrev_out */
+#define PANDA_NTT_INVERSE_BITREV_IN 3u  /* ..._inverse_bitrev_in */
+#define PANDA_NTT_COSET 4u              /* ..._coset */
+#define PANDA_NTT_COSET_INVERSE 5u      /* ..._coset_inverse */
+panda_error panda_ntt_execute_batch(unsigned field, unsigned kind, const panda_ntt_configuration_v1 exec_cfg, unsigned batch, const void *shift);
+/* How a batch runs (pure host arithmetic, no device call): *launches = the transform kernels one call enqueues once its tables are
+ * cached -- the passes of that kind and size (panda_ntt_pass_plan; the bit-reversed kinds keep the eight-bit plan at 2^18 / 2^27), plus
+ * one for a coset kind's sweep -- whatever `batch` is; *members_per_workgroup = the members one workgroup of the first pass carries (1 from
+ * 2^10 points on).  Either pointer may be NULL.  Invalid for the shapes panda_ntt_execute_batch refuses. */
+panda_error panda_ntt_batch_plan(unsigned log_n, unsigned kind, unsigned batch, unsigned *launches, unsigned *members_per_workgroup);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

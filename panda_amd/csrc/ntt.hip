@@ -293,8 +293,14 @@ struct PassArgs {
     unsigned br_out;      // last pass only: leave the output in bit-reversed order (y[k] goes to bitrev(k))
 };
 
-template <class Fr, int DEG>
-__global__ void __launch_bounds__(512) k_ntt_pass(PassArgs A)
+// One tile of a pass.  BATCH (panda_ntt_execute_batch, members of n = 2^log_n <= TILE points): the tile holds TILE / n WHOLE members --
+// member blockIdx.x * (TILE / n) + ml in elements [ml n, (ml + 1) n) of the tile and of LDS, fewer in the last workgroup of a ragged
+// batch -- so no thread idles because a member is short.  Every member is one contiguous run of n elements of x and of y; tile element
+// e = ml n + el maps to sub-transform and position by the single call's formulas on el with blk0 = 0 and B = n / R sub-transforms, and
+// only the member's base is added to the data addresses and ml n to the LDS index.  In LDS the tile is TE / R sub-transforms of R
+// elements either way, so the butterfly rounds do not know about members.
+template <class Fr, int DEG, bool BATCH>
+__device__ __forceinline__ void ntt_pass_tile(const PassArgs &A, unsigned batch)
 {
     constexpr unsigned R = 1u << DEG;
     __shared__ u32 s_u[NL * TilePlanes::STRIDE];
@@ -302,20 +308,28 @@ __global__ void __launch_bounds__(512) k_ntt_pass(PassArgs A)
     const TilePlanes u{s_u};
     const TwiddlePlanes pq{s_pq};
     const unsigned tid = threadIdx.x;
-    const unsigned TE = A.tile_elems;
-    const unsigned B = TE >> DEG;              // sub-transforms in this tile
     const unsigned S = (1u << A.log_n) >> DEG; // stride between the inputs of one sub-transform
+    const unsigned member0 = BATCH ? blockIdx.x * ((unsigned)TILE >> A.log_n) : 0u; // first member of this tile
+    const unsigned members_left = batch - member0; // >= 1: the grid has ceil(batch / (TILE >> log_n)) workgroups
+    const unsigned TE = BATCH ? (members_left < ((unsigned)TILE >> A.log_n) ? members_left : (unsigned)TILE >> A.log_n) << A.log_n : A.tile_elems;
+    const unsigned B = BATCH ? S : TE >> DEG; // sub-transforms in this tile (BATCH: in one member)
     const unsigned p = 1u << A.lgp;
-    const unsigned blk0 = blockIdx.x * B;
+    const unsigned blk0 = BATCH ? 0u : blockIdx.x * B;
 
     if (tid < (R >> 1)) {
         Fe<Fr> w;
         load_tw(w, A.pq, tid);
         pq.store(w, tid);
     }
-    for (unsigned e = tid; e < TE; e += 512) {
-        unsigned b, i;
-        size_t src_index;
+    for (unsigned te = tid; te < TE; te += 512) {
+        unsigned b, i, e = te, lds_member = 0;
+        size_t src_index, member_base = 0;
+        if constexpr (BATCH) {
+            const unsigned ml = te >> A.log_n;
+            e = te & ((1u << A.log_n) - 1);
+            lds_member = ml << A.log_n;
+            member_base = (size_t)(member0 + ml) << A.log_n;
+        }
         if (A.br_in) {
             // element j = blk + i*S of the natural order sits at bitrev(j) = (bitrev(blk) << DEG) + bitrev(i): the 2^DEG inputs of
             // a sub-transform are one contiguous run, read in storage order and dropped into LDS at their natural index
@@ -330,7 +344,7 @@ __global__ void __launch_bounds__(512) k_ntt_pass(PassArgs A)
         }
         const unsigned blk = blk0 + b;
         Fe<Fr> v;
-        load_elem(v, A.x + src_index * 8);
+        load_elem(v, A.x + (member_base + src_index) * 8);
         if (A.lgp != 0 || A.force_tw) {
             const unsigned k = blk & (p - 1);
             if (k * i != 0 || A.force_tw) {
@@ -353,7 +367,7 @@ __global__ void __launch_bounds__(512) k_ntt_pass(PassArgs A)
                 fe_mul(v, v, tw);
             }
         }
-        u.store(v, b * R + i);
+        u.store(v, lds_member + b * R + i);
     }
     __syncthreads();
 
@@ -369,9 +383,15 @@ __global__ void __launch_bounds__(512) k_ntt_pass(PassArgs A)
 
     constexpr int FB = Rounds<Fr, DEG, 0, 2>::FINAL;
     static_assert(FB < 512, "final bound must fit fe_reduce_small (values below 2^9 p)");
-    for (unsigned e = tid; e < TE; e += 512) {
-        unsigned b, i, lds_i;
-        size_t dst_index;
+    for (unsigned te = tid; te < TE; te += 512) {
+        unsigned b, i, lds_i, e = te, lds_member = 0;
+        size_t dst_index, member_base = 0;
+        if constexpr (BATCH) {
+            const unsigned ml = te >> A.log_n;
+            e = te & ((1u << A.log_n) - 1);
+            lds_member = ml << A.log_n;
+            member_base = (size_t)(member0 + ml) << A.log_n;
+        }
         if (A.br_out) {
             // last pass (lgp + DEG == log_n, or a single pass): y[blk + i p] goes to bitrev(blk + i p) = (bitrev(blk) << DEG) + bitrev(i);
             // LDS holds the outputs in bit-reversed order already, so a sub-transform leaves as one contiguous run, copied straight out
@@ -397,11 +417,24 @@ __global__ void __launch_bounds__(512) k_ntt_pass(PassArgs A)
             lds_i = bitrev(i, DEG);
         }
         Fe<Fr> v;
-        u.load(v, b * R + lds_i);
+        u.load(v, lds_member + b * R + lds_i);
         fe_reduce_small_2p(v);
         if (A.canonical) fe_reduce_once(v); // between passes < 2p is enough: it fits the 32 bytes and the next pass's bounds
-        store_elem(A.y + dst_index * 8, v);
+        store_elem(A.y + (member_base + dst_index) * 8, v);
     }
+}
+
+template <class Fr, int DEG>
+__global__ void __launch_bounds__(512) k_ntt_pass(PassArgs A)
+{
+    ntt_pass_tile<Fr, DEG, false>(A, 1);
+}
+
+// the same pass over `batch` members of 2^log_n <= TILE points, TILE >> log_n members per workgroup
+template <class Fr, int DEG>
+__global__ void __launch_bounds__(512) k_ntt_pass_batch(PassArgs A, unsigned batch)
+{
+    ntt_pass_tile<Fr, DEG, true>(A, batch);
 }
 
 // x[i] *= ta[i & 0xffff] * tb[i >> 16]   (the inter-slab twiddle w^(r k2) of the multi-GPU transform)
@@ -421,6 +454,27 @@ __global__ void __launch_bounds__(256) k_slab_twiddle(u32 *__restrict__ x, const
     fe_mul(v, v, tw);
     fe_reduce_once(v);
     store_elem(x + (size_t)i * 8, v);
+}
+
+// x[g] *= ta[i & 0xffff] * tb[i >> 16], i = g mod 2^log_n: the coset sweep of a batch, one launch over all members, the table index
+// being the element's index within its member
+template <class Fr>
+__global__ void __launch_bounds__(256) k_member_twiddle(u32 *__restrict__ x, const u32 *__restrict__ ta, const u32 *__restrict__ tb, unsigned log_n, unsigned count)
+{
+    const unsigned g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= count) return;
+    const unsigned i = g & ((1u << log_n) - 1);
+    Fe<Fr> v, tw;
+    load_elem(v, x + (size_t)g * 8);
+    load_tw(tw, ta, i & 0xffffu);
+    if (i >> 16) {
+        Fe<Fr> t2;
+        load_tw(t2, tb, i >> 16);
+        fe_mul(tw, tw, t2);
+    }
+    fe_mul(v, v, tw);
+    fe_reduce_once(v);
+    store_elem(x + (size_t)g * 8, v);
 }
 
 // ------------------------------------------------------------------------------- host side
@@ -566,11 +620,19 @@ void build_table2(hipStream_t stream, const Fe<Fr> &base, const Fe<Fr> *scale, u
 // LDS planes per exchange batch and resident workgroups per CU of k_ntt_pass8 (5 planes: 40 KB + 10 KB of twiddles, three fit)
 constexpr int P8_PLANES = 5, P8_MINW = 3;
 
+// batched = true: the instantiations with a member dimension; `tiles` then counts the tiles of all members
 template <class Fr>
-void launch_pass8(bool first, bool last, const panda_ntt8::Pass8Args &a, unsigned tiles, hipStream_t s)
+void launch_pass8(bool first, bool last, const panda_ntt8::Pass8Args &a, unsigned tiles, hipStream_t s, bool batched = false)
 {
     using namespace panda_ntt8;
-    if (last)
+    if (batched) {
+        if (last)
+            hipLaunchKernelGGL((k_ntt_pass8<Fr, false, true, P8_PLANES, P8_MINW, true>), dim3(tiles), dim3(THREADS), 0, s, a);
+        else if (first)
+            hipLaunchKernelGGL((k_ntt_pass8<Fr, true, false, P8_PLANES, P8_MINW, true>), dim3(tiles), dim3(THREADS), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_ntt_pass8<Fr, false, false, P8_PLANES, P8_MINW, true>), dim3(tiles), dim3(THREADS), 0, s, a);
+    } else if (last)
         hipLaunchKernelGGL((k_ntt_pass8<Fr, false, true, P8_PLANES, P8_MINW>), dim3(tiles), dim3(THREADS), 0, s, a);
     else if (first)
         hipLaunchKernelGGL((k_ntt_pass8<Fr, true, false, P8_PLANES, P8_MINW>), dim3(tiles), dim3(THREADS), 0, s, a);
@@ -582,10 +644,17 @@ void launch_pass8(bool first, bool last, const panda_ntt8::Pass8Args &a, unsigne
 constexpr int P9_PLANES = 3, P9_MINW = 3;
 
 template <class Fr>
-void launch_pass9(bool first, bool last, const panda_ntt8::Pass8Args &a, unsigned tiles, hipStream_t s)
+void launch_pass9(bool first, bool last, const panda_ntt8::Pass8Args &a, unsigned tiles, hipStream_t s, bool batched = false)
 {
     using namespace panda_ntt8;
-    if (last)
+    if (batched) {
+        if (last)
+            hipLaunchKernelGGL((k_ntt_pass9<Fr, false, true, P9_PLANES, P9_MINW, true>), dim3(tiles), dim3(THREADS), 0, s, a);
+        else if (first)
+            hipLaunchKernelGGL((k_ntt_pass9<Fr, true, false, P9_PLANES, P9_MINW, true>), dim3(tiles), dim3(THREADS), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_ntt_pass9<Fr, false, false, P9_PLANES, P9_MINW, true>), dim3(tiles), dim3(THREADS), 0, s, a);
+    } else if (last)
         hipLaunchKernelGGL((k_ntt_pass9<Fr, false, true, P9_PLANES, P9_MINW>), dim3(tiles), dim3(THREADS), 0, s, a);
     else if (first)
         hipLaunchKernelGGL((k_ntt_pass9<Fr, true, false, P9_PLANES, P9_MINW>), dim3(tiles), dim3(THREADS), 0, s, a);
@@ -595,10 +664,20 @@ void launch_pass9(bool first, bool last, const panda_ntt8::Pass8Args &a, unsigne
 
 // short last pass / size-G slab transforms in registers (radix 2, 4, 8): d_pq holds max(1, 2^(deg-1)) precomputed-quotient entries
 template <class Fr>
-void launch_small(unsigned deg, const u32 *x, u32 *y, const u32 *d_pq, unsigned log_count, bool br_out, hipStream_t s)
+void launch_small(unsigned deg, const u32 *x, u32 *y, const u32 *d_pq, unsigned log_count, bool br_out, hipStream_t s, unsigned batch = 0)
 {
     using namespace panda_ntt8;
     const SmallArgs a{x, y, d_pq, log_count, br_out ? 1u : 0u};
+    if (batch) { // members of 2^11 points and more: 2^log_count is a multiple of the 256 threads, the grid covers the batch exactly
+        const unsigned blocks = (unsigned)((((u64)batch << log_count) + 255) / 256);
+        if (deg == 1)
+            hipLaunchKernelGGL((k_ntt_small<Fr, 1, true>), dim3(blocks), dim3(256), 0, s, a);
+        else if (deg == 2)
+            hipLaunchKernelGGL((k_ntt_small<Fr, 2, true>), dim3(blocks), dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_ntt_small<Fr, 3, true>), dim3(blocks), dim3(256), 0, s, a);
+        return;
+    }
     const unsigned blocks = (unsigned)((((u64)1 << log_count) + 255) / 256);
     if (deg == 1)
         hipLaunchKernelGGL((k_ntt_small<Fr, 1>), dim3(blocks), dim3(256), 0, s, a);
@@ -620,6 +699,25 @@ void launch_pass(unsigned deg, const PassArgs &a, unsigned tiles, hipStream_t s)
     case 6: hipLaunchKernelGGL((k_ntt_pass<Fr, 6>), dim3(tiles), dim3(512), 0, s, a); break;
     case 7: hipLaunchKernelGGL((k_ntt_pass<Fr, 7>), dim3(tiles), dim3(512), 0, s, a); break;
     default: hipLaunchKernelGGL((k_ntt_pass<Fr, 8>), dim3(tiles), dim3(512), 0, s, a); break;
+    }
+}
+
+// how many whole members of 2^log_n points one workgroup of k_ntt_pass_batch carries
+unsigned members_per_workgroup(unsigned log_n) { return log_n < 10 ? (unsigned)TILE >> log_n : 1u; }
+
+template <class Fr>
+void launch_pass_batch(unsigned deg, const PassArgs &a, unsigned batch, hipStream_t s)
+{
+    const unsigned mpw = members_per_workgroup(a.log_n), tiles = (batch + mpw - 1) / mpw;
+    switch (deg) {
+    case 1: hipLaunchKernelGGL((k_ntt_pass_batch<Fr, 1>), dim3(tiles), dim3(512), 0, s, a, batch); break;
+    case 2: hipLaunchKernelGGL((k_ntt_pass_batch<Fr, 2>), dim3(tiles), dim3(512), 0, s, a, batch); break;
+    case 3: hipLaunchKernelGGL((k_ntt_pass_batch<Fr, 3>), dim3(tiles), dim3(512), 0, s, a, batch); break;
+    case 4: hipLaunchKernelGGL((k_ntt_pass_batch<Fr, 4>), dim3(tiles), dim3(512), 0, s, a, batch); break;
+    case 5: hipLaunchKernelGGL((k_ntt_pass_batch<Fr, 5>), dim3(tiles), dim3(512), 0, s, a, batch); break;
+    case 6: hipLaunchKernelGGL((k_ntt_pass_batch<Fr, 6>), dim3(tiles), dim3(512), 0, s, a, batch); break;
+    case 7: hipLaunchKernelGGL((k_ntt_pass_batch<Fr, 7>), dim3(tiles), dim3(512), 0, s, a, batch); break;
+    default: hipLaunchKernelGGL((k_ntt_pass_batch<Fr, 8>), dim3(tiles), dim3(512), 0, s, a, batch); break;
     }
 }
 
@@ -804,9 +902,11 @@ thread_local PassTimer g_pass_timer;
 // multiplies every output (folded into the last pass's twiddles).  Leaves the result in src when *passes_out
 // is even, in dst when odd; enqueues only.
 // `build` = false reuses the tables already sitting in `arena` (same carve order).
+// `batch` != 0: src and dst hold that many transforms, member after member, and every pass is launched ONCE over all of them by the
+// kernels' instantiations with a member dimension (tables, plan and flag are those of one member); 0: the single call's kernels.
 template <class Fr, class Alloc>
 hipError_t ntt_passes(hipStream_t stream, Alloc &arena, const u32 *src, u32 *dst, const Fe<Fr> &omega, unsigned log_n, const Fe<Fr> *scale,
-                      unsigned *passes_out, bool build = true, bool br_in = false, bool br_out = false, unsigned streamed = 0)
+                      unsigned *passes_out, bool build = true, bool br_in = false, bool br_out = false, unsigned streamed = 0, unsigned batch = 0)
 {
     const u64 n = (u64)1 << log_n;
     unsigned log_p = 0, passes = 0;
@@ -870,17 +970,18 @@ hipError_t ntt_passes(hipStream_t stream, Alloc &arena, const u32 *src, u32 *dst
                     }
                 }
             }
+            const unsigned tiles = (unsigned)(n / panda_ntt8::ELEMS) * std::max(batch, 1u); // batch * n <= 2^28: at most 2^17 tiles
             if (deg == 9)
-                launch_pass9<Fr>(passes == 0, last, a, (unsigned)(n / panda_ntt8::ELEMS), stream);
+                launch_pass9<Fr>(passes == 0, last, a, tiles, stream, batch != 0);
             else
-                launch_pass8<Fr>(passes == 0, last, a, (unsigned)(n / panda_ntt8::ELEMS), stream);
+                launch_pass8<Fr>(passes == 0, last, a, tiles, stream, batch != 0);
         } else if (regs8 && last && deg <= 3) {
             // a short last pass behind k_ntt_pass8 (its twiddle is already on the data): radix 2 / 4 / 8 in registers
             if (build) {
                 fe_pow_u64(base, omega, n >> deg);
                 build_table2<Fr>(stream, base, nullptr, std::max(1u, (1u << deg) >> 1), d_pq);
             }
-            launch_small<Fr>(deg, src, dst, d_pq, log_n - deg, br_out, stream);
+            launch_small<Fr>(deg, src, dst, d_pq, log_n - deg, br_out, stream, batch);
         } else {
             PassArgs a{};
             a.x = src;
@@ -917,7 +1018,10 @@ hipError_t ntt_passes(hipStream_t stream, Alloc &arena, const u32 *src, u32 *dst
                     build_table<Fr>(stream, base, scale, 1, d_ta); // single pass: the table is just the scale
                 }
             }
-            launch_pass<Fr>(deg, a, (unsigned)(n / a.tile_elems), stream);
+            if (batch)
+                launch_pass_batch<Fr>(deg, a, batch, stream); // log_n < 11: a member fits a tile
+            else
+                launch_pass<Fr>(deg, a, (unsigned)(n / a.tile_elems), stream);
         }
         PANDA_TRY(hipGetLastError());
         const u32 *tmp = dst;
@@ -1059,6 +1163,144 @@ hipError_t ntt_coset_run(const panda_ntt_configuration_v1 &cfg, const void *shif
     fe_inv(gi, g);
     u32 *res = (*(unsigned *)cfg.flag & 1u) ? (u32 *)cfg.d_dst : (u32 *)cfg.d_src;
     return scale_by_powers<Fr>(stream, res, cfg.log_n, gi);
+}
+
+// ---- batches: many transforms of one size, field, kind and root in one call (panda_ntt_execute_batch)
+constexpr unsigned KIND_INVERSE = PANDA_NTT_INVERSE, KIND_BITREV_OUT = PANDA_NTT_BITREV_OUT,
+                   KIND_INVERSE_BITREV_IN = PANDA_NTT_INVERSE_BITREV_IN, KIND_COSET = PANDA_NTT_COSET, KIND_COSET_INVERSE = PANDA_NTT_COSET_INVERSE;
+constexpr unsigned BATCH_MAX_LOG_ELEMS = 28; // batch * 2^log_n: the index range the kernels are proven on
+
+bool batch_kind_inverse(unsigned kind) { return kind == KIND_INVERSE || kind == KIND_INVERSE_BITREV_IN || kind == KIND_COSET_INVERSE; }
+bool batch_shape_invalid(unsigned kind, unsigned log_n, unsigned batch)
+{
+    return kind > KIND_COSET_INVERSE || batch == 0 || batch > PANDA_NTT_MAX_BATCH || log_n > 28 || ((u64)batch << log_n) > ((u64)1 << BATCH_MAX_LOG_ELEMS);
+}
+
+// power tables of a batch's coset sweep (g^j, or g^-j for the inverse), per host thread, keyed by field, size, direction and shift: a
+// prover's round shifts every polynomial by the same generator
+thread_local TwiddleCache g_coset_tables;
+
+// `batch` transforms of 2^log_n points, member j at element offset j 2^log_n of d_src / d_dst: one table set (the single call's, under the
+// single call's key), every pass launched once over all members, the coset kinds' shift as ONE sweep over the batch in front of
+// (forward) or behind (inverse) the passes, one synchronisation.  The caller has checked the shape and the pointers.
+template <class Fr>
+hipError_t ntt_run_batch(hipStream_t stream, void *d_src, void *d_dst, const u32 *omega_wire, unsigned log_n, unsigned *flag, unsigned kind, unsigned batch,
+                         const u32 *shift_wire)
+{
+    const bool inverse = batch_kind_inverse(kind), br_in = kind == KIND_INVERSE_BITREV_IN, br_out = kind == KIND_BITREV_OUT;
+    const bool coset = kind == KIND_COSET || kind == KIND_COSET_INVERSE;
+    Fe<Fr> g;
+    fe_zero(g);
+    if (coset) {
+        fe_from_wire(g, shift_wire);
+        if (fe_is_zero_mod_p(g)) return hipErrorInvalidValue;
+    }
+    const size_t bytes = ((size_t)batch << log_n) * 32;
+    if (panda::extent_too_short(d_src, bytes) || panda::extent_too_short(d_dst, bytes)) return hipErrorInvalidValue;
+    PANDA_TRY(order_after_null_stream(stream));
+    u32 key[12];
+    int dev = -1;
+    PANDA_TRY(hipGetDevice(&dev));
+    // the whole-transform tables of ONE member, looked up and built exactly as ntt_run does
+    const unsigned mode = g_streamed_tables.load(std::memory_order_relaxed);
+    unsigned streamed = mode == STREAMED_FAIL_ALLOC ? STREAMED_POLICY : mode, streamed_bits = 0;
+    const PassPlan pl = plan_passes(log_n, br_in, br_out);
+    for (unsigned j = 0; j < pl.count; j++) streamed_bits = std::max(streamed_bits, streamed_table_bits(pl, j, log_n, streamed));
+    if (!streamed_bits || (g_streamed_unavailable.device == dev && streamed_bits >= g_streamed_unavailable.bits)) streamed = 0;
+    const unsigned variant = (inverse ? 1u : 0u) | (br_in ? 2u : 0u) | (br_out ? 4u : 0u);
+    twiddle_key<Fr>(key, log_n, variant | (streamed << 3), omega_wire);
+    unsigned slot = g_whole_last ^ 1u;
+    for (unsigned c = 0; c < 2; c++) {
+        const TwiddleCache &t = g_twiddles[TW_WHOLE + c];
+        if (t.valid && t.device == dev && memcmp(key, t.key, sizeof(key)) == 0) slot = c;
+    }
+    g_whole_last = slot;
+    TwiddleCache &tw = g_twiddles[TW_WHOLE + slot];
+    PANDA_TRY(tw.settle(stream));
+    const bool hit = tw.valid && tw.device == dev && memcmp(key, tw.key, sizeof(key)) == 0;
+    Fe<Fr> omega, scale;
+    fe_zero(omega);
+    fe_zero(scale);
+    if (!hit) {
+        fe_from_wire(omega, omega_wire);
+        if (inverse) inverse_parameters<Fr>(omega, scale, (u64)1 << log_n);
+        hipError_t got = (streamed && mode == STREAMED_FAIL_ALLOC) ? hipErrorOutOfMemory : tw.ensure(passes_table_bytes(log_n, br_in, br_out, streamed) + 4096);
+        if (got == hipErrorOutOfMemory && streamed) { // as ntt_run: this size runs with the two small tables from now on
+            (void)hipGetLastError();
+            if (g_streamed_unavailable.device != dev) g_streamed_unavailable = StreamedUnavailable{dev, streamed_bits};
+            g_streamed_unavailable.bits = std::min(g_streamed_unavailable.bits, streamed_bits);
+            streamed = 0;
+            twiddle_key<Fr>(key, log_n, variant, omega_wire);
+            got = tw.ensure(passes_table_bytes(log_n, br_in, br_out, 0) + 4096);
+        }
+        PANDA_TRY(got);
+        g_table_builds++;
+    } else
+        tw.used = 0;
+    tw.valid = false;
+    // the sweep's tables: ta[j] = g^j, j < min(n, 2^16); tb[j] = g^(2^16 j), j < n / 2^16
+    TwiddleCache &ct = g_coset_tables;
+    u32 ckey[12];
+    u32 *d_ca = nullptr, *d_cb = nullptr;
+    if (coset) {
+        twiddle_key<Fr>(ckey, log_n, inverse ? 1u : 0u, shift_wire);
+        const bool chit = ct.valid && ct.device == dev && memcmp(ckey, ct.key, sizeof(ckey)) == 0;
+        if (!chit)
+            PANDA_TRY(ct.ensure(SZ_TA + SZ_TB + 4096));
+        else
+            ct.used = 0;
+        ct.valid = false;
+        d_ca = (u32 *)ct.take(SZ_TA);
+        d_cb = (u32 *)ct.take(SZ_TB);
+        if (!d_ca || !d_cb) return hipErrorOutOfMemory;
+        if (!chit) {
+            Fe<Fr> base = g;
+            if (inverse) fe_inv(base, g);
+            build_table<Fr>(stream, base, nullptr, (unsigned)std::min<u64>((u64)1 << log_n, 1u << 16), d_ca);
+            if (log_n > 16) {
+                Fe<Fr> base_b;
+                fe_pow_u64(base_b, base, (u64)1 << 16);
+                build_table<Fr>(stream, base_b, nullptr, 1u << (log_n - 16), d_cb);
+            }
+            PANDA_TRY(hipGetLastError());
+        }
+    }
+    const unsigned count = batch << log_n, sweep_blocks = (count + 255) / 256;
+    unsigned passes = 0;
+    PassTimer &pt = g_pass_timer;
+    const bool stamps = panda::clock_stamps_enabled();
+    uint64_t *stamp_block = nullptr;
+    panda::thread_ntt_clock() = panda::ClockDelta{};
+    if (stamps) {
+        PANDA_TRY(panda::thread_stamp_blocks(&stamp_block));
+        stamp_block += 2 * 2 * panda::CLOCK_STAMP_SLOTS;
+        for (unsigned i = 0; i < 2 * 2 * panda::CLOCK_STAMP_SLOTS; i++) stamp_block[i] = 0;
+    }
+    if (coset && !inverse) {
+        hipLaunchKernelGGL(k_member_twiddle<Fr>, dim3(sweep_blocks), dim3(256), 0, stream, (u32 *)d_src, d_ca, d_cb, log_n, count);
+        PANDA_TRY(hipGetLastError());
+    }
+    PANDA_TRY(pt.begin(stream));
+    if (stamps) PANDA_TRY(panda::enqueue_clock_stamp(stream, stamp_block));
+    PANDA_TRY(ntt_passes<Fr>(stream, tw, (const u32 *)d_src, (u32 *)d_dst, omega, log_n, inverse ? &scale : nullptr, &passes, !hit, br_in, br_out, streamed, batch));
+    if (stamps) PANDA_TRY(panda::enqueue_clock_stamp(stream, stamp_block + 2 * panda::CLOCK_STAMP_SLOTS));
+    PANDA_TRY(pt.end(stream));
+    if (coset && inverse) {
+        hipLaunchKernelGGL(k_member_twiddle<Fr>, dim3(sweep_blocks), dim3(256), 0, stream, (passes & 1u) ? (u32 *)d_dst : (u32 *)d_src, d_ca, d_cb, log_n, count);
+        PANDA_TRY(hipGetLastError());
+    }
+    *flag = passes & 1u;
+    PANDA_TRY(hipStreamSynchronize(stream));
+    pt.read();
+    if (stamps) panda::thread_ntt_clock() = panda::clock_delta(stamp_block, stamp_block + 2 * panda::CLOCK_STAMP_SLOTS);
+    memcpy(tw.key, key, sizeof(key));
+    tw.valid = true; // only after the tables are known to be complete
+    tw.has_pending = false;
+    if (coset) {
+        memcpy(ct.key, ckey, sizeof(ckey));
+        ct.valid = true;
+    }
+    return hipSuccess;
 }
 
 // a rank's slab and scratch hold 2^(log_n - log_ranks) elements each (log_n >= log_ranks checked by the callers)
@@ -1425,6 +1667,30 @@ panda_error panda_ntt_slab_inverse_step2_bls12_381_enqueue(const panda_ntt_slab_
     return static_cast<panda_error>(slab_inverse_local<Bls381Fr>(cfg, false));
 }
 
+// Many transforms of one size in one call: see include/panda_interface.h.  The shape and pointer checks come before any runtime call.
+panda_error panda_ntt_execute_batch(unsigned field, unsigned kind, const panda_ntt_configuration_v1 cfg, unsigned batch, const void *shift)
+{
+    if (field > 2 || batch_shape_invalid(kind, cfg.log_n, batch) || !cfg.d_src || !cfg.d_dst || !cfg.d_omega || !cfg.flag) return panda_error_invalid_value;
+    if ((kind == KIND_COSET || kind == KIND_COSET_INVERSE) && !shift) return panda_error_invalid_value;
+    hipStream_t stream = static_cast<hipStream_t>(cfg.stream.handle);
+    const u32 *omega = (const u32 *)cfg.d_omega, *g = (const u32 *)shift;
+    unsigned *flag = (unsigned *)cfg.flag;
+    switch (field) {
+    case 0: return static_cast<panda_error>(ntt_run_batch<Bn254Fr>(stream, cfg.d_src, cfg.d_dst, omega, cfg.log_n, flag, kind, batch, g));
+    case 1: return static_cast<panda_error>(ntt_run_batch<Bls377Fr>(stream, cfg.d_src, cfg.d_dst, omega, cfg.log_n, flag, kind, batch, g));
+    default: return static_cast<panda_error>(ntt_run_batch<Bls381Fr>(stream, cfg.d_src, cfg.d_dst, omega, cfg.log_n, flag, kind, batch, g));
+    }
+}
+
+panda_error panda_ntt_batch_plan(unsigned log_n, unsigned kind, unsigned batch, unsigned *launches, unsigned *members_per_wg)
+{
+    if (batch_shape_invalid(kind, log_n, batch)) return panda_error_invalid_value;
+    const PassPlan pl = plan_passes(log_n, kind == KIND_INVERSE_BITREV_IN, kind == KIND_BITREV_OUT);
+    if (launches) *launches = pl.count + ((kind == KIND_COSET || kind == KIND_COSET_INVERSE) ? 1u : 0u);
+    if (members_per_wg) *members_per_wg = members_per_workgroup(log_n);
+    return panda_success;
+}
+
 panda_error panda_ntt_last_clock(uint64_t *out)
 {
     if (!out) return panda_error_invalid_value;
@@ -1471,6 +1737,7 @@ panda_error panda_ntt_tear_down(void)
     g_omega_set = false;
     g_streamed_unavailable = StreamedUnavailable{};
     for (auto &t : g_twiddles) (void)t.release();
+    (void)g_coset_tables.release();
     return static_cast<panda_error>(panda::release_thread_arena());
 }
 

@@ -229,7 +229,10 @@ __device__ __forceinline__ void exchange(Fe<Fr> (&e)[8], u32 *s_x, const unsigne
 #define P8_B_UNIFORM true
 #endif
 
-template <class Fr, bool FIRST, bool LAST, int PB, int MINW>
+// BATCH (panda_ntt_execute_batch): the grid covers `batch` members of 2^log_n points each, member after member in x and in y;
+// blockIdx.x = member * (n / ELEMS) + tile.  A tile belongs to one member, every index below stays member-local, and the member's
+// base -- wave-uniform, so it lives in scalar registers -- is added to the two data pointers only.  All tables are shared.
+template <class Fr, bool FIRST, bool LAST, int PB, int MINW, bool BATCH = false>
 __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass8(Pass8Args A)
 {
     constexpr const Plan8<Fr, FIRST ? 2 : 3> &PL = plan8_v<Fr, FIRST ? 2 : 3>;
@@ -242,6 +245,19 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass8(Pass8Args A)
     const unsigned skip = LAST ? A.skip : 0u, deg = 8 - skip;
     const unsigned S = (1u << A.log_n) >> deg; // stride between the inputs of one sub-transform
     const unsigned lgp = A.lgp;
+    const u32 *xin = A.x;
+    u32 *yout = A.y;
+    unsigned tile_of_member = blockIdx.x;
+    if constexpr (BATCH) {
+#ifdef P8_PERSIST
+        static_assert(!BATCH, "the persistent-tile experiment has no member dimension");
+#endif
+        const unsigned log_tiles = A.log_n - 11; // ELEMS = 2^11; BATCH runs members of 2^11 points and more
+        const size_t member_words = ((size_t)(blockIdx.x >> log_tiles) << A.log_n) * 8;
+        xin += member_words;
+        yout += member_words;
+        tile_of_member = blockIdx.x & ((1u << log_tiles) - 1);
+    }
 
     // butterfly twiddles of block A -> LDS (2560 words, ten per thread)
     {
@@ -255,7 +271,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass8(Pass8Args A)
   for (unsigned tile = blockIdx.x; tile < A.tiles; tile += gridDim.x) {
 #else
   {
-    const unsigned tile = blockIdx.x;
+    const unsigned tile = tile_of_member;
 #endif
     const unsigned blk0 = tile * (SUBS << skip);
 
@@ -272,14 +288,14 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass8(Pass8Args A)
             s = (lane >> 5) | (wave << 1);
             base = ((size_t)brev0(blk0 + s, A.log_n - 8) << 8) + (bi << 3);
 #pragma unroll
-            for (int m = 0; m < 8; m++) load_elem32(e[m], A.x + (base + br3(m)) * 8);
+            for (int m = 0; m < 8; m++) load_elem32(e[m], xin + (base + br3(m)) * 8);
         } else if (skip == 0) {
             s = lane & 7;
             i0 = (lane >> 3) | (wave << 3);
             base = (size_t)(blk0 + s) + (size_t)i0 * S;
             step = (size_t)32 * S;
 #pragma unroll
-            for (int m = 0; m < 8; m++) load_elem32(e[m], A.x + (base + m * step) * 8);
+            for (int m = 0; m < 8; m++) load_elem32(e[m], xin + (base + m * step) * 8);
         } else { // local index i8 = i0 + 32 m: its top `skip` bits pick the sub-transform (8 apart), the rest the position
             s = lane & 7;
             i0 = (lane >> 3) | (wave << 3);
@@ -287,7 +303,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass8(Pass8Args A)
 #pragma unroll
             for (int m = 0; m < 8; m++) {
                 const unsigned i8 = i0 + 32 * m;
-                load_elem32(e[m], A.x + ((size_t)(blk0 + ((i8 >> deg) << 3) + s) + (size_t)(i8 & mask) * S) * 8);
+                load_elem32(e[m], xin + ((size_t)(blk0 + ((i8 >> deg) << 3) + s) + (size_t)(i8 & mask) * S) * 8);
             }
         }
     }
@@ -415,7 +431,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass8(Pass8Args A)
             const unsigned v = (br3(m) << 5) | iq;                        // bitrev8 of the local index 8 q + m
             const unsigned sub = blk0 + (brev0(v & smask, skip) << 3) + s; // its top `skip` bits, un-reversed, pick the sub-transform
             const size_t dst = A.br_out ? ((size_t)brev0(sub, lgp) << deg) + ((8 * q + m) & pmask) : (size_t)sub + ((size_t)(v >> skip) << lgp);
-            store_elem32(A.y + dst * 8, e[m]);
+            store_elem32(yout + dst * 8, e[m]);
         }
     } else {
         const size_t base = ((size_t)(blk - k) << 8) + k + ((size_t)iq << lgp);
@@ -444,7 +460,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass8(Pass8Args A)
                 } else
                     fe_norm(x, e[m]); // the last round leaves its outputs un-normalised (limbs < 3 * 2^30): a Montgomery product wants them below 2^30.5
                 fe_mul(v, x, tw); // x < FB p, tw < p: below 0.9 R p; the result is tight and below 2p: it fits the 32-byte element and the next pass's input bound
-                store_elem32(A.y + (base + ((size_t)(br3(m) << 5) << lgp)) * 8, v);
+                store_elem32(yout + (base + ((size_t)(br3(m) << 5) << lgp)) * 8, v);
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else if (A.cb == 0) { // one table: lgp == 0, k2 = i_out
@@ -457,7 +473,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass8(Pass8Args A)
                 if (m + 1 < 8) load_tw2(nxt, A.ta, row | ((br3(m + 1) << 5) | iq));
                 Fe<Fr> v;
                 fe_mul_shoup<Fr, false>(v, e[m], t.w, t.q);
-                store_elem32(A.y + (base + ((size_t)(br3(m) << 5) << lgp)) * 8, v);
+                store_elem32(yout + (base + ((size_t)(br3(m) << 5) << lgp)) * 8, v);
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else { // k2 = i_out 2^lgp + k: the low ca (<= lgp) bits are the thread's, the rest the element's
@@ -473,7 +489,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass8(Pass8Args A)
                 Fe<Fr> v, u;
                 fe_mul_shoup<Fr, false>(u, e[m], t.w, t.q);
                 fe_mul_shoup<Fr, false>(v, u, ta.w, ta.q);
-                store_elem32(A.y + (base + ((size_t)(br3(m) << 5) << lgp)) * 8, v);
+                store_elem32(yout + (base + ((size_t)(br3(m) << 5) << lgp)) * 8, v);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -496,17 +512,27 @@ struct SmallArgs {
     unsigned br_out;
 };
 
-template <class Fr, int DEG>
+// BATCH: the grid covers batch * S threads exactly (S >= 256 there: members of 2^11 points and more); thread g owns sub-transform
+// g mod S of member g / S.
+template <class Fr, int DEG, bool BATCH = false>
 __global__ void __launch_bounds__(256) k_ntt_small(SmallArgs A)
 {
     static_assert(DEG >= 1 && DEG <= 3, "radix 2, 4 or 8");
     constexpr int R = 1 << DEG;
     const size_t S = (size_t)1 << A.log_count;
-    const size_t blk = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (blk >= S) return;
+    size_t blk = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 *xin = A.x;
+    u32 *yout = A.y;
+    if constexpr (BATCH) {
+        const size_t member = blk >> A.log_count;
+        blk &= S - 1;
+        xin += ((member << A.log_count) << DEG) * 8;
+        yout += ((member << A.log_count) << DEG) * 8;
+    } else if (blk >= S)
+        return;
     Fe<Fr> e[R];
 #pragma unroll
-    for (int i = 0; i < R; i++) load_elem32(e[i], A.x + (blk + i * S) * 8);
+    for (int i = 0; i < R; i++) load_elem32(e[i], xin + (blk + i * S) * 8);
     // bounds 3 -> 7 -> 15 -> 31 (each round at most doubles and adds one): far below R / p for every supported field
     TwV<Fr> t;
     if constexpr (DEG == 1) {
@@ -539,7 +565,7 @@ __global__ void __launch_bounds__(256) k_ntt_small(SmallArgs A)
         fe_reduce_once(e[i]);
         const unsigned i_out = (unsigned)(DEG == 1 ? i : (DEG == 2 ? (((i & 1) << 1) | (i >> 1)) : br3(i)));
         const size_t dst = A.br_out ? ((size_t)brev0((unsigned)blk, A.log_count) << DEG) + i : blk + i_out * S;
-        store_elem32(A.y + dst * 8, e[i]);
+        store_elem32(yout + dst * 8, e[i]);
     }
 }
 

@@ -57,7 +57,8 @@ struct Plan9 {
 template <class Fr, int B0>
 inline constexpr Plan9<Fr, B0> plan9_v{};
 
-template <class Fr, bool FIRST, bool LAST, int PB, int MINW>
+// BATCH: a member dimension in the grid, as in k_ntt_pass8 (blockIdx.x = member * (n / ELEMS) + tile).
+template <class Fr, bool FIRST, bool LAST, int PB, int MINW, bool BATCH = false>
 __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass9(Pass8Args A)
 {
     constexpr const Plan9<Fr, FIRST ? 2 : 3> &PL = plan9_v<Fr, FIRST ? 2 : 3>;
@@ -67,7 +68,17 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass9(Pass8Args A)
     const unsigned tid = threadIdx.x;
     const unsigned lane = tid & 63;
     const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned blk0 = blockIdx.x * SUBS9;
+    const u32 *xin = A.x;
+    u32 *yout = A.y;
+    unsigned tile = blockIdx.x;
+    if constexpr (BATCH) {
+        const unsigned log_tiles = A.log_n - 11;
+        const size_t member_words = ((size_t)(blockIdx.x >> log_tiles) << A.log_n) * 8;
+        xin += member_words;
+        yout += member_words;
+        tile = blockIdx.x & ((1u << log_tiles) - 1);
+    }
+    const unsigned blk0 = tile * SUBS9;
     const unsigned S = (1u << A.log_n) >> 9; // stride between the inputs of one sub-transform
     const unsigned lgp = A.lgp;
 
@@ -86,7 +97,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass9(Pass8Args A)
     {
         const size_t base = (size_t)(blk0 + s) + (size_t)i0 * S, step = (size_t)64 * S;
 #pragma unroll
-        for (int m = 0; m < 8; m++) load_elem32(e[m], A.x + (base + m * step) * 8);
+        for (int m = 0; m < 8; m++) load_elem32(e[m], xin + (base + m * step) * 8);
     }
     __syncthreads(); // s_tw complete
     {
@@ -185,7 +196,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass9(Pass8Args A)
         for (int m = 0; m < 8; m++) {
             fe_reduce_mad_2p(e[m]);
             fe_reduce_once(e[m]);
-            store_elem32(A.y + (base + ((size_t)(br3(m) << 6) << lgp)) * 8, e[m]);
+            store_elem32(yout + (base + ((size_t)(br3(m) << 6) << lgp)) * 8, e[m]);
         }
     } else {
         const unsigned i2 = (blk >> lgp) >> A.i2_shift;
@@ -209,7 +220,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass9(Pass8Args A)
                 } else
                     fe_norm(x, e[m]);
                 fe_mul(v, x, tw);
-                store_elem32(A.y + (base + ((size_t)(br3(m) << 6) << lgp)) * 8, v);
+                store_elem32(yout + (base + ((size_t)(br3(m) << 6) << lgp)) * 8, v);
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else if (A.cb == 0) { // one table: lgp == 0, k2 = i_out
@@ -222,7 +233,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass9(Pass8Args A)
                 if (m + 1 < 8) load_tw2(nxt, A.ta, row | ((br3(m + 1) << 6) | iq));
                 Fe<Fr> v;
                 fe_mul_shoup<Fr, false>(v, e[m], t.w, t.q);
-                store_elem32(A.y + (base + ((size_t)(br3(m) << 6) << lgp)) * 8, v);
+                store_elem32(yout + (base + ((size_t)(br3(m) << 6) << lgp)) * 8, v);
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else { // k2 = i_out 2^lgp + k: the low ca (<= lgp) bits are the thread's, the rest the element's
@@ -238,7 +249,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_ntt_pass9(Pass8Args A)
                 Fe<Fr> v, u;
                 fe_mul_shoup<Fr, false>(u, e[m], t.w, t.q);
                 fe_mul_shoup<Fr, false>(v, u, ta.w, ta.q);
-                store_elem32(A.y + (base + ((size_t)(br3(m) << 6) << lgp)) * 8, v);
+                store_elem32(yout + (base + ((size_t)(br3(m) << 6) << lgp)) * 8, v);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }

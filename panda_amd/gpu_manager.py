@@ -513,3 +513,37 @@ def panda_ntt_bn254_gpu_bitrev(gm: PandaGpuManager, scalars: np.ndarray, omega, 
     natural-order coefficients with n^-1 fused.  In place on the caller's buffer like panda_ntt_bn254_gpu_v1."""
     lib = ffi.load()
     return _ntt(gm, scalars, log_n, lib.panda_ntt_execute_bn254_inverse_bitrev_in if inverse else lib.panda_ntt_execute_bn254_bitrev_out, omega)
+
+
+def panda_ntt_gpu_batch(gm: PandaGpuManager, polys, omega, log_n: int, field: int = 0, kind: int = 0, shift=None) -> int:
+    """Additive: transforms of one size, field (0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr), kind (ffi.NTT_FORWARD ...) and root in ONE
+    library call (panda_ntt_execute_batch).  The equal-length host arrays are staged into one device buffer, member after member, and
+    each is overwritten in place with its result, which is what the single call of that kind writes for it.  `shift` is the coset
+    generator of the coset kinds.  Returns the flag; an empty list returns 0 without a call."""
+    bufs = [_as_bytes(p) for p in polys]
+    if not bufs:
+        return 0
+    size = (1 << log_n) * FIELD_ELEMENT_LEN
+    if any(b.size != size for b in bufs):
+        raise PandaGpuError("SchedulingErr")
+    lib = ffi.load()
+    o = _as_bytes(omega)
+    g = _as_bytes(shift) if shift is not None else None
+    d_src, d_dst = C.c_void_p(), C.c_void_p()
+    flag = C.c_uint(0)
+    try:
+        ffi.check(lib.panda_malloc(C.byref(d_src), len(bufs) * size), "AsyncPoolMallocErr")
+        ffi.check(lib.panda_malloc(C.byref(d_dst), len(bufs) * size), "AsyncPoolMallocErr")
+        for k, b in enumerate(bufs):
+            ffi.check(lib.panda_memcpy_async(C.c_void_p(d_src.value + k * size), _ptr(b), size, gm.h2d_stream.raw), "AsyncMemcopyErr")
+        gm.wait_h2d()
+        cfg = ffi.NttconfigurationV1(gm.mem_pool, gm.exec_stream.raw, d_src, d_dst, _ptr(o), log_n, C.pointer(flag))
+        ffi.check(lib.panda_ntt_execute_batch(field, kind, cfg, len(bufs), _ptr(g) if g is not None else None), "SchedulingErr")
+        res = d_src.value if flag.value == 0 else d_dst.value
+        for k, b in enumerate(bufs):
+            ffi.check(lib.panda_memcpy(_ptr(b), C.c_void_p(res + k * size), size), "CreateContextError")
+    finally:
+        for d in (d_src, d_dst):
+            if d:
+                lib.panda_free(d)
+    return flag.value

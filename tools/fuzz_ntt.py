@@ -1,5 +1,5 @@
 """Randomised soak of the NTT entry points against the CPU oracle (development aid, not part of the suites).
-usage: fuzz_ntt.py <cases> [seed]"""
+usage: fuzz_ntt.py <cases> [seed] [--batch]   (--batch: every case also runs a random batch through panda_ntt_execute_batch)"""
 import os
 import sys
 import time
@@ -14,8 +14,10 @@ from panda_amd import gpu_manager as pgm  # noqa: E402
 
 
 def main():
-    cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-    rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+    batch_mode = "--batch" in sys.argv
+    argv = [v for v in sys.argv if v != "--batch"]
+    cases = int(argv[1]) if len(argv) > 1 else 100
+    rng = np.random.default_rng(int(argv[2]) if len(argv) > 2 else 1)
     gm = pgm.PandaGpuManager(0)
     calls = {po.F_BN254_FR: lambda b, om, k, inv: (pgm.panda_intt_bn254_gpu if inv else pgm.panda_ntt_bn254_gpu_v1)(gm, b, om, k),
              po.F_BLS377_FR: lambda b, om, k, inv: pgm.panda_ntt_bls12_377_gpu_v1(gm, b, om, k, inverse=inv),
@@ -37,6 +39,14 @@ def main():
         ok = (buf == po.ntt(fid, x, om, k)).all()
         calls[fid](buf, om, k, True)
         ok = ok and (buf == x).all()
+        if ok and batch_mode and k <= 16:  # x and up to eight random members in one call, forward then inverse, every member against the oracle
+            field = [po.F_BN254_FR, po.F_BLS377_FR, po.F_BLS381_FR].index(fid)
+            members = [x.copy()] + [po.gen_scalars(fid, int(rng.integers(1, 1 << 40)), 1 << k) for _ in range(int(rng.integers(1, 9)))]
+            orig = [m.copy() for m in members]
+            pgm.panda_ntt_gpu_batch(gm, members, om, k, field=field)
+            ok = all((m == po.ntt(fid, o, om, k)).all() for m, o in zip(members, orig))
+            pgm.panda_ntt_gpu_batch(gm, members, om, k, field=field, kind=1)
+            ok = ok and all((m == o).all() for m, o in zip(members, orig))
         if ok and fid == po.F_BN254_FR:  # the other BN254 orderings: bit-reversed output / input, and the sharded composition with its inverse
             want = po.ntt(fid, x, om, k)
             perm = np.array([int(format(i, f"0{k}b")[::-1], 2) if k else 0 for i in range(1 << k)])
