@@ -78,33 +78,24 @@ struct DigitsBatch {
     unsigned log_n, prefix_bit; // scalars per member (log2); c - 1 of the widest window
 };
 
-// scalar (Montgomery wire form) -> W signed digits.  code = (neg << SIGN) | (|d| - 1), ZERO for d = 0.
-// Replaces init_handle_scalars_kernel + the slice extraction of calc_lens/fill_arrs (msm_cuda.cuh:148-205,232-282);
-// the scalars are only read.  BATCH: code = (neg << SIGN) | (member << prefix_bit) | (|d| - 1).
-template <class Fr, class Code, bool BATCH = false>
-__global__ void __launch_bounds__(256) k_digits(const u32 *__restrict__ scalars, Code *__restrict__ dig, u64 n, panda::WindowPlan plan, panda::SampleCheck sc,
-                                                DigitsBatch bg)
+// The window plan as the digit loops read it: one LDS word per window, lo | width << 16.  Indexing the kernel argument itself by the
+// window number made every window of every scalar a pair of global loads, and the wait for them a wait for the digit store before it as
+// well: twelve memory round trips in sequence per scalar.  Every thread of the workgroup calls it; a barrier follows before the first use.
+__device__ __forceinline__ void stage_plan(u32 *wlo, const panda::WindowPlan &plan)
 {
-    typedef CodeTraits<Code> CT;
-    constexpr int L = Fr::L;
-    if (blockIdx.x == 0 && sc.wire) check_samples(sc);
-    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    u32 w[L], s[L + 1];
-    load_words<L>(w, scalars + i * L);
-    fe_wire_to_canonical<Fr>(s, w);
-    s[L] = 0;
+    for (unsigned k = threadIdx.x; k < plan.W; k += blockDim.x) wlo[k] = plan.lo[k] | ((u32)plan.width[k] << 16);
+}
+
+// canonical scalar s (s[L] = 0) -> its W signed digits in window order: f(k, code), code = (neg << SIGN) | prefix | (|d| - 1), ZERO for
+// d = 0.  The windows are walked word by word of the scalar (a plan's windows ascend: make_window_plan), so that the word index is a
+// constant of the unrolled outer loop and s[] stays in registers without an indexed move per window.
+template <int L, class CT, class Fn>
+__device__ __forceinline__ void for_each_digit(const u32 *s, const u32 *wlo, unsigned W, u32 prefix, Fn f)
+{
     u32 carry = 0;
-    const u32 prefix = BATCH ? (u32)(i >> bg.log_n) << bg.prefix_bit : 0u;
-    for (unsigned k = 0; k < plan.W; k++) {
-        const unsigned c = plan.width[k];
-        const u32 half = 1u << (c - 1), full = 1u << c, mask = full - 1;
-        unsigned lo = plan.lo[k], m = lo >> 5, sh = lo & 31;
-        u32 raw = 0;
-        if (m < (unsigned)L) {
-            u64 v = s[m] | ((u64)s[m + 1] << 32);
-            raw = (u32)(v >> sh) & mask;
-        }
+    unsigned k = 0;
+    auto digit = [&](u32 raw, unsigned c) {
+        const u32 half = 1u << (c - 1), full = 1u << c;
         raw += carry;
         u32 code;
         if (raw >= half) { // negative digit raw - 2^c (or zero when raw == 2^c)
@@ -115,8 +106,43 @@ __global__ void __launch_bounds__(256) k_digits(const u32 *__restrict__ scalars,
             carry = 0;
             code = raw ? (prefix | (raw - 1)) : CT::ZERO;
         }
-        dig[(u64)k * n + i] = (Code)code;
+        f(k, code);
+    };
+#pragma unroll
+    for (int m = 0; m < L; m++) {
+        const u64 v = s[m] | ((u64)s[m + 1] << 32);
+        while (k < W) {
+            const u32 e = __builtin_amdgcn_readfirstlane(wlo[k]);
+            const unsigned lo = e & 0xffffu, c = e >> 16;
+            if ((lo >> 5) != (unsigned)m) break;
+            digit((u32)(v >> (lo & 31)) & ((1u << c) - 1), c);
+            k++;
+        }
     }
+    for (; k < W; k++) digit(0, __builtin_amdgcn_readfirstlane(wlo[k]) >> 16); // windows above the scalar's words: the carry alone
+}
+
+// scalar (Montgomery wire form) -> W signed digits.
+// Replaces init_handle_scalars_kernel + the slice extraction of calc_lens/fill_arrs (msm_cuda.cuh:148-205,232-282);
+// the scalars are only read.  BATCH: code = (neg << SIGN) | (member << prefix_bit) | (|d| - 1).
+template <class Fr, class Code, bool BATCH = false>
+__global__ void __launch_bounds__(256) k_digits(const u32 *__restrict__ scalars, Code *__restrict__ dig, u64 n, panda::WindowPlan plan, panda::SampleCheck sc,
+                                                DigitsBatch bg)
+{
+    typedef CodeTraits<Code> CT;
+    constexpr int L = Fr::L;
+    __shared__ u32 wlo[panda::MAX_WINDOWS];
+    if (blockIdx.x == 0 && sc.wire) check_samples(sc);
+    stage_plan(wlo, plan);
+    __syncthreads();
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 w[L], s[L + 1];
+    load_words<L>(w, scalars + i * L);
+    fe_wire_to_canonical<Fr>(s, w);
+    s[L] = 0;
+    const u32 prefix = BATCH ? (u32)(i >> bg.log_n) << bg.prefix_bit : 0u;
+    for_each_digit<L, CT>(s, wlo, plan.W, prefix, [&](unsigned k, u32 code) { dig[(u64)k * n + i] = (Code)code; });
 }
 
 // k_digits and the level-1 histogram (k_part_hist) in one pass over the scalars: a block takes one tile of SORT_TILE
@@ -133,41 +159,27 @@ __global__ void __launch_bounds__(1024) k_digits_hist(const u32 *__restrict__ sc
     typedef CodeTraits<Code> CT;
     constexpr int L = Fr::L;
     extern __shared__ u32 hist[]; // [W][H]
+    __shared__ u32 wlo[panda::MAX_WINDOWS];
     if (blockIdx.x == 0 && sc.wire) check_samples(sc);
     const unsigned tile = blockIdx.x, tid = threadIdx.x;
     const unsigned WH = plan.W * g.H, threads = blockDim.x;
     for (unsigned i = tid; i < WH; i += threads) hist[i] = 0;
+    stage_plan(wlo, plan);
     __syncthreads();
     const u64 begin = (u64)tile * SORT_TILE, end = begin + SORT_TILE < n ? begin + SORT_TILE : n;
+    // a thread walks its scalars one after the other; the next one's words are on their way while this one's digits are cut and stored
+    u32 w[L];
+    if (begin + tid < end) load_words<L>(w, scalars + (begin + tid) * L);
     for (u64 i = begin + tid; i < end; i += threads) {
-        u32 w[L], s[L + 1];
-        load_words<L>(w, scalars + i * L);
+        u32 s[L + 1];
         fe_wire_to_canonical<Fr>(s, w);
+        if (i + threads < end) load_words<L>(w, scalars + (i + threads) * L);
         s[L] = 0;
-        u32 carry = 0;
         const u32 prefix = BATCH ? (u32)(i >> bg.log_n) << bg.prefix_bit : 0u;
-        for (unsigned k = 0; k < plan.W; k++) {
-            const unsigned c = plan.width[k];
-            const u32 half = 1u << (c - 1), full = 1u << c, mask = full - 1;
-            unsigned lo = plan.lo[k], m = lo >> 5, sh = lo & 31;
-            u32 raw = 0;
-            if (m < (unsigned)L) {
-                u64 v = s[m] | ((u64)s[m + 1] << 32);
-                raw = (u32)(v >> sh) & mask;
-            }
-            raw += carry;
-            u32 code;
-            if (raw >= half) {
-                u32 mag = full - raw;
-                carry = 1;
-                code = mag ? ((1u << CT::SIGN) | prefix | (mag - 1)) : CT::ZERO;
-            } else {
-                carry = 0;
-                code = raw ? (prefix | (raw - 1)) : CT::ZERO;
-            }
+        for_each_digit<L, CT>(s, wlo, plan.W, prefix, [&](unsigned k, u32 code) {
             dig[(u64)k * n + i] = (Code)code;
             if (code != CT::ZERO) atomicAdd(&hist[k * g.H + ((code & CT::MAG) >> g.lo_bits)], 1u);
-        }
+        });
     }
     __syncthreads();
     for (unsigned i = tid; i < WH; i += threads) {
@@ -249,146 +261,196 @@ __global__ void __launch_bounds__(1024) k_part_scan_cols(const u32 *__restrict__
     if (lane == 0) totals[(u64)w * g.H + h] = run;
 }
 
+// inclusive scan over the workgroup of one value per thread: shuffles inside a wave, the wave totals through `wsum` (one LDS word per
+// wave) and ONE barrier -- a Hillis-Steele scan over 1024 threads is ten steps of two barriers each, and the scatter kernels scan in every
+// one of their ~25 000 workgroups.  Every thread of the workgroup must call it; `wsum` must not be in use across the call.
+__device__ __forceinline__ u32 block_inclusive_scan(u32 v, u32 *wsum)
+{
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const u32 up = __shfl_up(v, d, 64);
+        if (lane >= d) v += up;
+    }
+    if (lane == 63) wsum[wave] = v;
+    __syncthreads();
+    for (unsigned w = 0; w < wave; w++) v += wsum[w]; // broadcast reads, at most 15
+    return v;
+}
+
 // one block per window: exclusive scan of the H column totals -> part_off[w][0..H]
 __global__ void __launch_bounds__(1024) k_part_offsets(const u32 *__restrict__ totals, u32 *__restrict__ part_off, SortGeom g)
 {
-    __shared__ u32 tot[MAX_PARTS];
+    __shared__ u32 wsum[16];
     const unsigned w = blockIdx.x, t = threadIdx.x;
     const u32 mine = t < g.H ? totals[(u64)w * g.H + t] : 0;
-    tot[t] = mine;
-    __syncthreads();
-    for (unsigned d = 1; d < 1024; d <<= 1) {
-        u32 v = (t >= d) ? tot[t - d] : 0;
-        __syncthreads();
-        tot[t] += v;
-        __syncthreads();
-    }
-    if (t < g.H) part_off[(u64)w * (g.H + 1) + t] = tot[t] - mine;
-    if (t == 1023) part_off[(u64)w * (g.H + 1) + g.H] = tot[1023];
+    const u32 inc = block_inclusive_scan(mine, wsum);
+    if (t < g.H) part_off[(u64)w * (g.H + 1) + t] = inc - mine;
+    if (t == 1023) part_off[(u64)w * (g.H + 1) + g.H] = inc;
 }
 
-// block-wide exclusive scan of `count` LDS words in place by THREADS threads
-template <unsigned THREADS = SORT_THREADS>
-__device__ __forceinline__ void block_exclusive_scan(u32 *a, unsigned count, u32 *scratch /* THREADS words */)
-{
-    const unsigned tid = threadIdx.x;
-    const unsigned per = (count + THREADS - 1) / THREADS;
-    u32 local = 0;
-    for (unsigned j = 0; j < per; j++) {
-        unsigned i = tid * per + j;
-        if (i < count) local += a[i];
-    }
-    scratch[tid] = local;
-    __syncthreads();
-    for (unsigned d = 1; d < THREADS; d <<= 1) {
-        u32 v = (tid >= d) ? scratch[tid - d] : 0;
-        __syncthreads();
-        scratch[tid] += v;
-        __syncthreads();
-    }
-    u32 run = scratch[tid] - local;
-    for (unsigned j = 0; j < per; j++) {
-        unsigned i = tid * per + j;
-        if (i < count) {
-            u32 v = a[i];
-            a[i] = run;
-            run += v;
+// 16-byte loads of a tile's codes issued ahead of their use: a scatter workgroup sends them out first, so that they travel while it
+// reads its counts and scans them, and ranks from registers afterwards (for_each_code's order and its one-code-per-load fallback)
+template <class Code, unsigned THREADS>
+struct TileCodes {
+    static constexpr unsigned PER = 16 / sizeof(Code), LOADS = SORT_TILE / (THREADS * PER);
+    static_assert(LOADS * THREADS * PER == SORT_TILE, "whole loads");
+    uint4 v[LOADS];
+    bool vec;
+    __device__ __forceinline__ void load(const Code *__restrict__ dw, u64 begin, u64 end)
+    {
+        vec = !(reinterpret_cast<uintptr_t>(dw + begin) & 15);
+        if (!vec) return;
+#pragma unroll
+        for (unsigned q = 0; q < LOADS; q++) {
+            const u64 a = begin + ((u64)q * THREADS + threadIdx.x) * PER;
+            v[q] = a < end ? *reinterpret_cast<const uint4 *>(dw + a) : uint4{0, 0, 0, 0};
         }
     }
-    __syncthreads();
-}
+    __device__ __forceinline__ u32 code(unsigned q, unsigned j) const
+    {
+        const u32 wv[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+        return sizeof(Code) == 2 ? (wv[j >> 1] >> (16 * (j & 1))) & 0xffffu : wv[j];
+    }
+    // slot = rank(index, code) for every code of the thread, then place(index, code, slot) for every code: the LDS atomics of a thread's
+    // entries go out one behind the other and their answers are waited for once, instead of once per entry
+    template <class Rank, class Place>
+    __device__ __forceinline__ void rank_and_place(const Code *__restrict__ dw, u64 begin, u64 end, Rank rank, Place place) const
+    {
+        if (!vec) {
+            for_each_code<Code>(dw, begin, end, [&](u64 i, u32 c) { place(i, c, rank(i, c)); });
+            return;
+        }
+        u32 slot[LOADS * PER];
+#pragma unroll
+        for (unsigned q = 0; q < LOADS; q++) {
+            const u64 a = begin + ((u64)q * THREADS + threadIdx.x) * PER;
+#pragma unroll
+            for (unsigned j = 0; j < PER; j++)
+                if (a + j < end) slot[q * PER + j] = rank(a + j, code(q, j));
+        }
+#pragma unroll
+        for (unsigned q = 0; q < LOADS; q++) {
+            const u64 a = begin + ((u64)q * THREADS + threadIdx.x) * PER;
+#pragma unroll
+            for (unsigned j = 0; j < PER; j++)
+                if (a + j < end) place(a + j, code(q, j), slot[q * PER + j]);
+        }
+    }
+};
 
 // word written to the partition buffer: [lo : lo_bits][sign : 1][point id : log_n].
 // The tile is first grouped by partition in LDS (local counting sort), then written out linearly, so that a wave
 // stores runs of consecutive addresses instead of 64 unrelated words.
+// Per entry the kernel touches LDS six times: the cursor (which starts at the partition's local offset, so that the atomic returns the
+// staging slot itself), the word and its partition on the way in; the partition, `delta` (global position minus local offset of the
+// partition's run: destination = delta + slot) and the word on the way out.
 template <class Code, class Word>
 __global__ void __launch_bounds__(SORT_THREADS) k_part_scatter(const Code *__restrict__ dig, const u32 *__restrict__ tile_hist, const u32 *__restrict__ tile_pref,
                                                       const u32 *__restrict__ part_off, Word *__restrict__ p1, SortGeom g)
 {
     typedef CodeTraits<Code> CT;
-    __shared__ u32 lstart[MAX_PARTS]; // local start of each partition's run in the staging buffer
-    __shared__ u32 lcur[MAX_PARTS];   // local cursor
-    __shared__ u32 gbase[MAX_PARTS];  // global position of this tile's first element of the partition
+    static_assert(MAX_PARTS <= SORT_THREADS, "a partition counter per thread");
+    __shared__ u32 lcur[MAX_PARTS];  // cursor into the staging buffer; the end of the partition's run once the tile is ranked
+    __shared__ u32 delta[MAX_PARTS]; // global position of this tile's first element of the partition, minus the local start of its run
     __shared__ Word words[SORT_TILE];
     __shared__ uint16_t parts_of[SORT_TILE];
-    __shared__ u32 scratch[SORT_THREADS];
+    __shared__ u32 wsum[SORT_THREADS / 64];
     const unsigned w = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
     const u64 row = ((u64)w * g.tiles + tile) * g.H;
     const u32 *po = part_off + (u64)w * (g.H + 1);
-    for (unsigned i = tid; i < g.H; i += SORT_THREADS) {
-        lstart[i] = tile_hist[row + i]; // this tile's count, turned into a local offset by the scan below
-        lcur[i] = 0;
-        gbase[i] = po[i] + tile_pref[row + i];
-    }
-    __syncthreads();
     const u64 n = (u64)1 << g.log_n;
     const Code *dw = dig + ((u64)w << g.log_n);
     Word *pw = p1 + ((u64)w << g.log_n);
     const u64 begin = (u64)tile * SORT_TILE, end = begin + SORT_TILE < n ? begin + SORT_TILE : n;
     const u32 lo_mask = (1u << g.lo_bits) - 1;
-    block_exclusive_scan(lstart, g.H, scratch);
-    for_each_code<Code>(dw, begin, end, [&](u64 i, u32 code) {
-        if (code == CT::ZERO) return;
-        u32 b = code & CT::MAG, h = b >> g.lo_bits;
-        u32 slot = lstart[h] + atomicAdd(&lcur[h], 1u);
-        words[slot] = ((Word)(b & lo_mask) << (g.log_n + 1)) | (Word)(((code >> CT::SIGN) << g.log_n) | (u32)i);
-        parts_of[slot] = (uint16_t)h;
-    });
-    __syncthreads();
-    const u32 total = lstart[g.H - 1] + lcur[g.H - 1];
-    for (u32 j = tid; j < total; j += SORT_THREADS) {
-        u32 h = parts_of[j];
-        pw[gbase[h] + (j - lstart[h])] = words[j];
+    TileCodes<Code, SORT_THREADS> codes;
+    codes.load(dw, begin, end);
+    const u32 count = tid < g.H ? tile_hist[row + tid] : 0; // this tile's count, turned into a local offset by the scan
+    const u32 gbase = tid < g.H ? po[tid] + tile_pref[row + tid] : 0;
+    const u32 lstart = block_inclusive_scan(count, wsum) - count;
+    if (tid < g.H) {
+        lcur[tid] = lstart;
+        delta[tid] = gbase - lstart;
     }
+    __syncthreads();
+    codes.rank_and_place(
+        dw, begin, end, [&](u64, u32 code) -> u32 { return code == CT::ZERO ? 0u : atomicAdd(&lcur[(code & CT::MAG) >> g.lo_bits], 1u); },
+        [&](u64 i, u32 code, u32 slot) {
+            if (code == CT::ZERO) return;
+            u32 b = code & CT::MAG, h = b >> g.lo_bits;
+            words[slot] = ((Word)(b & lo_mask) << (g.log_n + 1)) | (Word)(((code >> CT::SIGN) << g.log_n) | (u32)i);
+            parts_of[slot] = (uint16_t)h;
+        });
+    __syncthreads();
+    const u32 total = lcur[g.H - 1];
+    for (u32 j = tid; j < total; j += SORT_THREADS) pw[delta[parts_of[j]] + j] = words[j];
 }
 
 // Tabled mode, level 1: the same scatter, but the word is stored split -- a u32 [b3 key bits][sign][point id], which is
 // exactly the word level 2 hands on, and a u8 with the b2 key bits level 2 partitions by.  Level 2 then counts from the
 // byte array alone and never moves more than five bytes per entry.
+// The byte travels through LDS in one word with the entry's partition; on the way out four bytes that go to one aligned dword of p1_hi
+// (four neighbouring lanes inside one run) leave as that dword, the bytes at the ends of a run singly.
 template <class Code>
 __global__ void __launch_bounds__(SORT_THREADS) k1_scatter_split(const Code *__restrict__ dig, const u32 *__restrict__ tile_hist, const u32 *__restrict__ tile_pref,
                                                         const u32 *__restrict__ part_off, u32 *__restrict__ p1_lo, unsigned char *__restrict__ p1_hi, SortGeom g,
                                                         unsigned b3)
 {
     typedef CodeTraits<Code> CT;
-    __shared__ u32 lstart[MAX_PARTS];
-    __shared__ u32 lcur[MAX_PARTS];
-    __shared__ u32 gbase[MAX_PARTS];
+    static_assert(MAX_PARTS <= SORT_THREADS, "a partition counter per thread");
+    __shared__ u32 lcur[MAX_PARTS];  // as in k_part_scatter
+    __shared__ u32 delta[MAX_PARTS];
     __shared__ u32 words[SORT_TILE];
-    __shared__ unsigned char his[SORT_TILE];
-    __shared__ uint16_t parts_of[SORT_TILE];
-    __shared__ u32 scratch[SORT_THREADS];
-    const unsigned w = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    __shared__ u32 meta[SORT_TILE]; // partition << 8 | the b2 key bits
+    __shared__ u32 wsum[SORT_THREADS / 64];
+    const unsigned w = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
     const u64 row = ((u64)w * g.tiles + tile) * g.H;
     const u32 *po = part_off + (u64)w * (g.H + 1);
-    for (unsigned i = tid; i < g.H; i += SORT_THREADS) {
-        lstart[i] = tile_hist[row + i];
-        lcur[i] = 0;
-        gbase[i] = po[i] + tile_pref[row + i];
-    }
-    __syncthreads();
     const u64 n = (u64)1 << g.log_n;
     const Code *dw = dig + ((u64)w << g.log_n);
     u32 *plo = p1_lo + ((u64)w << g.log_n);
     unsigned char *phi = p1_hi + ((u64)w << g.log_n);
     const u64 begin = (u64)tile * SORT_TILE, end = begin + SORT_TILE < n ? begin + SORT_TILE : n;
     const u32 b3_mask = (1u << b3) - 1, b2_mask = (1u << (g.lo_bits - b3)) - 1;
-    block_exclusive_scan(lstart, g.H, scratch);
-    for_each_code<Code>(dw, begin, end, [&](u64 i, u32 code) {
-        if (code == CT::ZERO) return;
-        u32 b = code & CT::MAG, h = b >> g.lo_bits;
-        u32 slot = lstart[h] + atomicAdd(&lcur[h], 1u);
-        words[slot] = ((b & b3_mask) << (g.log_n + 1)) | ((code >> CT::SIGN) << g.log_n) | (u32)i;
-        his[slot] = (unsigned char)((b >> b3) & b2_mask);
-        parts_of[slot] = (uint16_t)h;
-    });
+    TileCodes<Code, SORT_THREADS> codes;
+    codes.load(dw, begin, end);
+    const u32 count = tid < g.H ? tile_hist[row + tid] : 0;
+    const u32 gbase = tid < g.H ? po[tid] + tile_pref[row + tid] : 0;
+    const u32 lstart = block_inclusive_scan(count, wsum) - count;
+    if (tid < g.H) {
+        lcur[tid] = lstart;
+        delta[tid] = gbase - lstart;
+    }
     __syncthreads();
-    const u32 total = lstart[g.H - 1] + lcur[g.H - 1];
-    for (u32 j = tid; j < total; j += SORT_THREADS) {
-        const u32 h = parts_of[j];
-        const u32 dst = gbase[h] + (j - lstart[h]);
-        plo[dst] = words[j];
-        phi[dst] = his[j];
+    codes.rank_and_place(
+        dw, begin, end, [&](u64, u32 code) -> u32 { return code == CT::ZERO ? 0u : atomicAdd(&lcur[(code & CT::MAG) >> g.lo_bits], 1u); },
+        [&](u64 i, u32 code, u32 slot) {
+            if (code == CT::ZERO) return;
+            u32 b = code & CT::MAG, h = b >> g.lo_bits;
+            words[slot] = ((b & b3_mask) << (g.log_n + 1)) | ((code >> CT::SIGN) << g.log_n) | (u32)i;
+            meta[slot] = (h << 8) | ((b >> b3) & b2_mask);
+        });
+    __syncthreads();
+    const u32 total = lcur[g.H - 1];
+    for (u32 base = 0; base < total; base += SORT_THREADS) { // uniform trip count: every lane takes part in the shuffles
+        const u32 j = base + tid;
+        const bool valid = j < total;
+        const u32 m = valid ? meta[j] : ~0u; // a partition no entry has
+        const u32 h = m >> 8;
+        u32 dst = 0;
+        if (valid) {
+            dst = delta[h] + j;
+            plo[dst] = words[j];
+        }
+        const u32 m1 = __shfl_down(m, 1, 64), m2 = __shfl_down(m, 2, 64), m3 = __shfl_down(m, 3, 64);
+        // lanes l .. l + 3 of one run hold consecutive destinations
+        const bool lead = valid && lane <= 60 && !(reinterpret_cast<uintptr_t>(phi + dst) & 3) && (m1 >> 8) == h && (m2 >> 8) == h && (m3 >> 8) == h;
+        const u64 leaders = __ballot(lead);
+        const bool covered = (((leaders << 1) | (leaders << 2) | (leaders << 3)) >> lane) & 1;
+        if (lead)
+            *reinterpret_cast<u32 *>(phi + dst) = (m & 0xffu) | ((m1 & 0xffu) << 8) | ((m2 & 0xffu) << 16) | (m3 << 24);
+        else if (valid && !covered)
+            phi[dst] = (unsigned char)m;
     }
 }
 
@@ -502,7 +564,7 @@ struct SortRange {
 // one workgroup: seg_tile[0..S] = exclusive prefix of ceil(len_s / SORT_TILE)
 __global__ void __launch_bounds__(SORT_THREADS) k2_seg_tiles(const u32 *__restrict__ part_off, u32 *__restrict__ seg_tile, TabledGeom g)
 {
-    __shared__ u32 scratch[SORT_THREADS];
+    __shared__ u32 wsum[SORT_THREADS / 64];
     const unsigned tid = threadIdx.x;
     const unsigned per = (g.S + SORT_THREADS - 1) / SORT_THREADS;
     u32 local = 0;
@@ -514,15 +576,8 @@ __global__ void __launch_bounds__(SORT_THREADS) k2_seg_tiles(const u32 *__restri
             local += (po[h1 + 1] - po[h1] + SORT_TILE - 1) / SORT_TILE;
         }
     }
-    scratch[tid] = local;
-    __syncthreads();
-    for (unsigned d = 1; d < SORT_THREADS; d <<= 1) {
-        u32 v = (tid >= d) ? scratch[tid - d] : 0;
-        __syncthreads();
-        scratch[tid] += v;
-        __syncthreads();
-    }
-    u32 run = scratch[tid] - local;
+    const u32 inc = block_inclusive_scan(local, wsum);
+    u32 run = inc - local;
     for (unsigned j = 0; j < per; j++) {
         unsigned s = tid * per + j;
         if (s < g.S) {
@@ -532,7 +587,7 @@ __global__ void __launch_bounds__(SORT_THREADS) k2_seg_tiles(const u32 *__restri
             run += (po[h1 + 1] - po[h1] + SORT_TILE - 1) / SORT_TILE;
         }
     }
-    if (tid == SORT_THREADS - 1) seg_tile[g.S] = scratch[SORT_THREADS - 1];
+    if (tid == SORT_THREADS - 1) seg_tile[g.S] = inc;
 }
 
 struct TileRange {
@@ -618,19 +673,12 @@ __global__ void __launch_bounds__(256) k2_scan_cols(const u32 *__restrict__ tile
 __global__ void __launch_bounds__(256) k2_offsets(const u32 *__restrict__ totals, u32 *__restrict__ sub_off, TabledGeom g, SortRange R)
 {
     __builtin_amdgcn_s_setprio(3); // beside the bucket accumulation of a split sort (SortSplit) these waves must win the issue arbitration: they issue little, it issues always
-    __shared__ u32 tot[256];
+    __shared__ u32 wsum[4];
     const unsigned s = R.s_lo + blockIdx.x, t = threadIdx.x;
     const u32 mine = t < g.H2 ? totals[(u64)s * g.H2 + t] : 0;
-    tot[t] = mine;
-    __syncthreads();
-    for (unsigned d = 1; d < 256; d <<= 1) {
-        u32 v = (t >= d) ? tot[t - d] : 0;
-        __syncthreads();
-        tot[t] += v;
-        __syncthreads();
-    }
-    if (t < g.H2) sub_off[(u64)s * (g.H2 + 1) + t] = tot[t] - mine;
-    if (t == 255) sub_off[(u64)s * (g.H2 + 1) + g.H2] = tot[255];
+    const u32 inc = block_inclusive_scan(mine, wsum);
+    if (t < g.H2) sub_off[(u64)s * (g.H2 + 1) + t] = inc - mine;
+    if (t == 255) sub_off[(u64)s * (g.H2 + 1) + g.H2] = inc;
 }
 
 // level-2 scatter: the u32 halves of the level-1 words, grouped by their u8 halves within the segment
@@ -642,51 +690,62 @@ __global__ void __launch_bounds__(THREADS) k2_scatter(const u32 *__restrict__ p1
                                                   const u32 *__restrict__ sub_off, u32 *__restrict__ p2, TabledGeom g, SortRange R)
 {
     __builtin_amdgcn_s_setprio(3); // beside the bucket accumulation of a split sort (SortSplit) these waves must win the issue arbitration: they issue little, it issues always
-    __shared__ u32 lstart[256], lcur[256];
-    __shared__ u64 gbase[256];
+    __shared__ u32 lcur[256];  // as in k_part_scatter
+    __shared__ u32 delta[256]; // positions in p2 fit 32 bits (sort3_supported: log_n + bits of W <= 31)
     __shared__ u32 words[SORT_TILE];
     __shared__ unsigned char parts_of[SORT_TILE];
-    __shared__ u32 scratch[THREADS];
+    __shared__ u32 wsum[THREADS / 64];
+    static_assert(THREADS >= 256, "a sub-partition counter per thread");
     const unsigned tid = threadIdx.x;
     unsigned tile;
     TileRange r;
     if (!locate_tile(r, tile, blockIdx.x, seg_tile, part_off, g, R)) return;
-    if (tid < 256) {
-        lstart[tid] = tid < g.H2 ? tile_hist[(u64)tile * g.H2 + tid] : 0;
-        lcur[tid] = 0;
-        if (tid < g.H2) gbase[tid] = r.seg_begin + sub_off[(u64)r.s * (g.H2 + 1) + tid] + tile_pref[(u64)tile * g.H2 + tid];
+    // 8 entries per thread and step: one aligned 8-byte vector of keys and the two 16-byte vectors of words that go with it (both arrays
+    // are padded, entries outside the tile are skipped by index).  With 1024 threads that is the whole tile in one step (and one more
+    // vector for thread 0 where the tile does not start on 8 entries); the loads of the first step go out before the counts are read and
+    // scanned, and are ranked from registers.
+    const u64 first = r.begin & ~(u64)7, a0 = first + (u64)tid * 8;
+    uint2 kv{0, 0};
+    uint4 w0{0, 0, 0, 0}, w1{0, 0, 0, 0};
+    if (a0 < r.end) {
+        kv = *reinterpret_cast<const uint2 *>(p1_hi + a0);
+        w0 = *reinterpret_cast<const uint4 *>(p1_lo + a0);
+        w1 = *reinterpret_cast<const uint4 *>(p1_lo + a0 + 4);
+    }
+    const u32 count = tid < g.H2 ? tile_hist[(u64)tile * g.H2 + tid] : 0;
+    const u32 gbase = tid < g.H2 ? (u32)r.seg_begin + sub_off[(u64)r.s * (g.H2 + 1) + tid] + tile_pref[(u64)tile * g.H2 + tid] : 0;
+    const u32 lstart = block_inclusive_scan(count, wsum) - count;
+    if (tid < g.H2) {
+        lcur[tid] = lstart;
+        delta[tid] = gbase - lstart;
     }
     __syncthreads();
-    block_exclusive_scan<THREADS>(lstart, g.H2, scratch);
-    // 16 entries per thread and step: one aligned 16-byte vector of keys and the four 16-byte vectors of words that go with
-    // it (both arrays are padded, entries outside the tile are skipped by index)
-    const u64 first = r.begin & ~(u64)15;
-    for (u64 a = first + (u64)tid * 16; a < r.end; a += (u64)THREADS * 16) {
-        const uint4 kv = *reinterpret_cast<const uint4 *>(p1_hi + a);
-        const u32 keys[4] = {kv.x, kv.y, kv.z, kv.w};
-        const uint4 *lo4 = reinterpret_cast<const uint4 *>(p1_lo + a);
+    for (u64 a = a0; a < r.end; a += (u64)THREADS * 8) {
+        if (a != a0) {
+            kv = *reinterpret_cast<const uint2 *>(p1_hi + a);
+            w0 = *reinterpret_cast<const uint4 *>(p1_lo + a);
+            w1 = *reinterpret_cast<const uint4 *>(p1_lo + a + 4);
+        }
+        const u32 keys[2] = {kv.x, kv.y};
+        const u32 ws[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+        u32 slot[8]; // the eight atomics go out one behind the other, their answers are waited for once
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint4 wv = lo4[q];
-            const u32 ws[4] = {wv.x, wv.y, wv.z, wv.w};
+        for (int j = 0; j < 8; j++) {
+            const u64 i = a + j;
+            if (i >= r.begin && i < r.end) slot[j] = atomicAdd(&lcur[(keys[j >> 2] >> (8 * (j & 3))) & 0xffu], 1u);
+        }
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const u64 i = a + 4 * q + j;
-                if (i >= r.begin && i < r.end) {
-                    const u32 h = (keys[q] >> (8 * j)) & 0xffu;
-                    const u32 slot = lstart[h] + atomicAdd(&lcur[h], 1u);
-                    words[slot] = ws[j];
-                    parts_of[slot] = (unsigned char)h;
-                }
+        for (int j = 0; j < 8; j++) {
+            const u64 i = a + j;
+            if (i >= r.begin && i < r.end) {
+                words[slot[j]] = ws[j];
+                parts_of[slot[j]] = (unsigned char)((keys[j >> 2] >> (8 * (j & 3))) & 0xffu);
             }
         }
     }
     __syncthreads();
     const u32 total = (u32)(r.end - r.begin);
-    for (u32 j = tid; j < total; j += THREADS) {
-        u32 h = parts_of[j];
-        p2[gbase[h] + (j - lstart[h])] = words[j];
-    }
+    for (u32 j = tid; j < total; j += THREADS) p2[delta[parts_of[j]] + j] = words[j];
 }
 
 // ---- tabled mode, level 3: merge the windows -------------------------------------------------------------------------
@@ -741,28 +800,17 @@ __global__ void __launch_bounds__(1024) k3_cell_counts(const u32 *__restrict__ s
 __global__ void __launch_bounds__(1024) k3_cell_offsets(const u32 *__restrict__ cell_cnt, const u32 *__restrict__ blk_sum, u32 *__restrict__ cell_off, TabledGeom g, SortRange R)
 {
     __builtin_amdgcn_s_setprio(3); // beside the bucket accumulation of a split sort (SortSplit) these waves must win the issue arbitration: they issue little, it issues always
-    __shared__ u32 red[1024];
-    __shared__ u32 sc[1024];
+    __shared__ u32 wsum[16], wsum_before[16], before;
     const unsigned blk = R.q_lo / 1024 + blockIdx.x, t = threadIdx.x, T = blockDim.x, per = 1024 / T;
     u32 v = 0;
     for (unsigned b = t; b < blk; b += T) v += blk_sum[b]; // the blocks of earlier launches included: their counts are complete (stream / event order)
-    red[t] = v;
     const unsigned q0 = blk * 1024 + t * per;
     u32 local = 0;
     for (unsigned j = 0; j < per; j++) local += q0 + j < R.q_hi ? cell_cnt[q0 + j] : 0;
-    sc[t] = local;
-    __syncthreads();
-    for (unsigned s = T >> 1; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    for (unsigned d = 1; d < T; d <<= 1) {
-        u32 u = (t >= d) ? sc[t - d] : 0;
-        __syncthreads();
-        sc[t] += u;
-        __syncthreads();
-    }
-    u32 run = red[0] + sc[t] - local;
+    v = block_inclusive_scan(v, wsum_before); // the last thread's is the sum
+    if (t == T - 1) before = v;
+    const u32 inc = block_inclusive_scan(local, wsum); // its barrier publishes `before`
+    u32 run = before + inc - local;
     for (unsigned j = 0; j < per; j++) {
         const unsigned q = q0 + j;
         if (q < R.q_hi) {
@@ -804,7 +852,6 @@ __global__ void __launch_bounds__(THREADS) k3_merge(const u32 *__restrict__ p2, 
     constexpr unsigned IMG = THREADS * K3_PER; // entries of the LDS image
     __shared__ u32 outbuf[IMG];
     __shared__ u64 rbegin[64];
-    __shared__ u32 rlen[64];
     __shared__ u32 vstart[65];
     const unsigned tid = threadIdx.x;
     // tabled mode: cell q of the one list, W runs to merge;  per-window mode: cell q of window k0's own list, one run
@@ -821,25 +868,24 @@ __global__ void __launch_bounds__(THREADS) k3_merge(const u32 *__restrict__ p2, 
     const bool closes_part = !g.per_window && cell + 1 == R.q_hi && q + 1 < g.Q;
     u32 *sw = sorted + ((u64)k0 << g.log_n);
     u32 *ow = off + (u64)k0 * (NB + 1);
-    if (tid < nruns) {
-        u64 b;
-        u32 len;
-        cell_run(b, len, k0 + tid, h1, h2, part_off, sub_off, g);
-        rbegin[tid] = b;
-        rlen[tid] = len;
+    if (tid < 64) { // the first wave: a run per lane (nruns <= 32), their prefix by shuffles
+        u64 b = 0;
+        u32 len = 0;
+        if (tid < nruns) {
+            cell_run(b, len, k0 + tid, h1, h2, part_off, sub_off, g);
+            rbegin[tid] = b;
+        }
+        u32 inc = len;
+        for (unsigned d = 1; d < 64; d <<= 1) {
+            const u32 up = __shfl_up(inc, d, 64);
+            if (tid >= d) inc += up;
+        }
+        if (tid < nruns) vstart[tid] = inc - len;
+        if (tid == nruns - 1) vstart[nruns] = inc;
     }
     if (tid < 128) cnt[tid] = 0;
     __syncthreads();
-    if (tid == 0) {
-        u32 run = 0;
-        for (unsigned k = 0; k < nruns; k++) {
-            vstart[k] = run;
-            run += rlen[k];
-        }
-        vstart[nruns] = run;
-    }
-    __syncthreads();
-    K3_STAMP(1); // setup: the runs of the cell, their prefix, two barriers
+    K3_STAMP(1); // setup: the runs of the cell, their prefix, one barrier
     const u32 N = vstart[nruns]; // uniform over the block
     const unsigned shift = g.log_n + 1;
     const u32 id_mask = (1u << g.log_n) - 1;
