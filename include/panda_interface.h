@@ -331,6 +331,39 @@ panda_error panda_ntt_execute_batch(unsigned field, unsigned kind, const panda_n
  * one for a coset kind's sweep -- whatever `batch` is; *members_per_workgroup = the members one workgroup of the first pass carries (1 from
  * 2^10 points on).  Either pointer may be NULL.  Invalid for the shapes panda_ntt_execute_batch refuses. */
 panda_error panda_ntt_batch_plan(unsigned log_n, unsigned kind, unsigned batch, unsigned *launches, unsigned *members_per_workgroup);
+/* Low-degree extension: `batch` polynomials of n = 2^log_n coefficients each to their evaluations on the coset g H_N of the domain of
+ * N = B n points, B = 2^log_blowup -- what a prover does to every wire, selector and permutation polynomial before it forms the quotient.
+ * f(g w_N^(i + B k)), k < n, is the n-point transform with root w_N^B of c_j (g w_N^i)^j, so the call runs B n-point members per
+ * polynomial (the batch's passes, one launch per pass over all of them) instead of one N-point transform of mostly zeros: log_blowup
+ * butterfly layers fewer, and no memset, copy or sweep over the zero padding.
+ *   field: 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr.  exec_cfg.log_n is the log of the COEFFICIENT count.
+ *   d_coeffs: device buffer of batch x n x 32 bytes, polynomial p at byte offset p x n x 32; read only.  exec_cfg.d_src and d_dst: device
+ *     buffers of batch x N x 32 bytes each, neither overlapping d_coeffs.  exec_cfg.d_omega: HOST pointer to the primitive N-th root w_N
+ *     of the EXTENDED domain (the members' root w_N^B is derived inside); `shift`: HOST pointer to g (32 bytes, Montgomery form, non-zero).
+ *   order PANDA_NTT_LDE_COSET_MAJOR: element (p B + i) n + k is f_p(g w_N^(i + B k)), i < B, k < n -- the B cosets of the small domain one
+ *     after the other; on coset i the vanishing polynomial X^n - 1 is the constant g^n w_N^(i n) - 1.
+ *   order PANDA_NTT_LDE_NATURAL: element p N + m is f_p(g w_N^m): byte for byte what panda_ntt_execute_<field>_coset writes for c_p
+ *     zero-padded to N points with root w_N and shift g (one more streaming kernel); the layout panda_ntt_execute_<field>_coset_inverse
+ *     at size N takes a quotient back to coefficients from.
+ *   *flag: 0 = the results are in d_src, 1 = in d_dst (panda_ntt_lde_plan tells in advance); the other buffer is scratch.  Outputs are
+ *     canonical.  Bytes behind the `batch` polynomials of any of the three buffers are never written.  Synchronous on return.
+ *   The members' twiddle tables are the calling thread's whole-transform cache under the single call's key for (log_n, forward, w_N^B): a
+ *     panda_ntt_execute_<field>_v1 call of 2^log_n points with that root after an extension builds nothing, and the other way round.  The
+ *     power tables of g are the ones a forward coset batch of 2^log_n points with that shift caches; those of w_N are cached by field,
+ *     log_n, log_blowup and root.  panda_ntt_last_device_ms / panda_ntt_last_clock report the passes.  log_n == 0 is legal.
+ *   panda_error_invalid_value, nothing launched, *flag untouched: field > 2, order > 1, log_blowup == 0 or > PANDA_NTT_LDE_MAX_LOG_BLOWUP,
+ *     batch == 0, batch x B > PANDA_NTT_MAX_BATCH, batch x N > 2^28 elements, log_n > 28, NULL d_coeffs / d_src / d_dst / d_omega / flag,
+ *     NULL or zero shift, d_coeffs overlapping d_src or d_dst as address ranges (all checked before any runtime call), and buffers of this
+ *     library's allocators shorter than stated. */
+#define PANDA_NTT_LDE_MAX_LOG_BLOWUP 4
+#define PANDA_NTT_LDE_COSET_MAJOR 0u
+#define PANDA_NTT_LDE_NATURAL 1u
+panda_error panda_ntt_execute_lde(unsigned field, const panda_ntt_configuration_v1 exec_cfg, const void *d_coeffs, unsigned log_blowup, unsigned batch,
+                                  const void *shift, unsigned order);
+/* How an extension runs (pure host arithmetic): *launches = 1 (expand) + the passes of 2^log_n points (panda_ntt_pass_plan) + 1 for the
+ * NATURAL order's interleave; *flag = the value panda_ntt_execute_lde will write, (passes + order) & 1.  Neither depends on `batch`.
+ * Either pointer may be NULL.  Invalid for the shapes panda_ntt_execute_lde refuses. */
+panda_error panda_ntt_lde_plan(unsigned log_n, unsigned log_blowup, unsigned batch, unsigned order, unsigned *launches, unsigned *flag);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

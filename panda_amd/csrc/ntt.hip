@@ -477,6 +477,65 @@ __global__ void __launch_bounds__(256) k_member_twiddle(u32 *__restrict__ x, con
     store_elem(x + (size_t)g * 8, v);
 }
 
+// Low-degree extension (panda_ntt_execute_lde), in front of the passes: coefficient j of polynomial p goes to the B = 2^log_b members
+// (p B + i) of 2^log_n points as c[p][j] (g w^i)^j, w the root of the B-times larger domain -- member i then transforms to the
+// evaluations on the coset g w^i of the small domain.  One thread per (p, j): t = g^j and u = w^j from two pairs of two-level power tables,
+// v_0 = c t, v_i = v_(i-1) u; one 32-byte load and B stores, each of them contiguous across the wave.  Stored canonical, as
+// k_member_twiddle leaves its elements for the passes.
+template <class Fr>
+__global__ void __launch_bounds__(256) k_lde_expand(const u32 *__restrict__ c, u32 *__restrict__ x, const u32 *__restrict__ ga, const u32 *__restrict__ gb,
+                                                    const u32 *__restrict__ wa, const u32 *__restrict__ wb, unsigned log_n, unsigned log_b, unsigned count)
+{
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const unsigned j = t & ((1u << log_n) - 1), p = t >> log_n;
+    Fe<Fr> v, tw, u;
+    load_elem(v, c + (size_t)t * 8);
+    load_tw(tw, ga, j & 0xffffu);
+    load_tw(u, wa, j & 0xffffu);
+    if (j >> 16) {
+        Fe<Fr> t2;
+        load_tw(t2, gb, j >> 16);
+        fe_mul(tw, tw, t2);
+        load_tw(t2, wb, j >> 16);
+        fe_mul(u, u, t2);
+    }
+    fe_mul(v, v, tw);
+    u32 *dst = x + ((((size_t)p << log_b) << log_n) + j) * 8;
+    const unsigned members = 1u << log_b;
+    for (unsigned i = 0;;) {
+        Fe<Fr> o = v;
+        fe_reduce_once(o);
+        store_elem(dst + ((size_t)i << log_n) * 8, o);
+        if (++i == members) break;
+        fe_mul(v, v, u);
+    }
+}
+
+// Low-degree extension, behind the passes of the NATURAL order: y[p][B k + i] = x[p][i][k], out of place.  One thread per (p, k): B
+// loads, each contiguous across the wave, all issued before the B stores of one contiguous run of 32 B bytes.  32-byte elements of any field.
+template <int LOG_B>
+__global__ void __launch_bounds__(256) k_lde_interleave(const u32 *__restrict__ x, u32 *__restrict__ y, unsigned log_n, unsigned count)
+{
+    constexpr unsigned B = 1u << LOG_B;
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const unsigned k = t & ((1u << log_n) - 1), p = t >> log_n;
+    const uint4 *src = reinterpret_cast<const uint4 *>(x) + ((((size_t)p << LOG_B) << log_n) + k) * 2;
+    uint4 lo[B], hi[B];
+#pragma unroll
+    for (unsigned i = 0; i < B; i++) {
+        lo[i] = src[((size_t)i << log_n) * 2];
+        hi[i] = src[((size_t)i << log_n) * 2 + 1];
+    }
+    uint4 *dst = reinterpret_cast<uint4 *>(y) + ((size_t)t << LOG_B) * 2;
+#pragma unroll
+    for (unsigned i = 0; i < B; i++) {
+        dst[2 * i] = lo[i];
+        dst[2 * i + 1] = hi[i];
+    }
+}
+
 // ------------------------------------------------------------------------------- host side
 
 std::mutex g_omega_mutex;
@@ -1045,16 +1104,28 @@ void inverse_parameters(Fe<Fr> &omega, Fe<Fr> &scale, u64 n)
     fe_reduce_once(scale);
 }
 
+// The whole-transform table set of a transform of 2^log_n points with root `omega_wire`, as the single call, the batch and the low-degree
+// extension all look it up: the calling thread's cache entry under the single call's key (field, size, direction and ordering, streamed
+// bit, root), the streamed-table policy with its out-of-memory fallback, and the host-side parameters when the tables have to be built
+// (`hit` false: the caller's ntt_passes builds them into `tw`).  The entry is left invalid; the caller publishes `key` once its stream
+// has been waited for.
 template <class Fr>
-hipError_t ntt_run(hipStream_t stream, void *d_src, void *d_dst, const u32 *omega_wire, unsigned log_n, unsigned *flag, bool inverse, bool br_in = false,
-                   bool br_out = false)
+struct WholeTables {
+    TwiddleCache *tw = nullptr;
+    bool hit = false;
+    unsigned streamed = 0;
+    int device = -1;
+    u32 key[12] = {0};
+    Fe<Fr> omega, scale;
+};
+
+template <class Fr>
+hipError_t whole_tables(hipStream_t stream, const u32 *omega_wire, unsigned log_n, bool inverse, bool br_in, bool br_out, WholeTables<Fr> &wt)
 {
-    if (log_n > 28 || !d_src || !d_dst || !omega_wire) return hipErrorInvalidValue;
-    if (panda::extent_too_short(d_src, (size_t)32 << log_n) || panda::extent_too_short(d_dst, (size_t)32 << log_n)) return hipErrorInvalidValue;
-    PANDA_TRY(order_after_null_stream(stream));
-    u32 key[12];
+    u32(&key)[12] = wt.key;
     int dev = -1;
     PANDA_TRY(hipGetDevice(&dev));
+    wt.device = dev;
     const unsigned mode = g_streamed_tables.load(std::memory_order_relaxed);
     unsigned streamed = mode == STREAMED_FAIL_ALLOC ? STREAMED_POLICY : mode, streamed_bits = 0;
     {
@@ -1072,9 +1143,10 @@ hipError_t ntt_run(hipStream_t stream, void *d_src, void *d_dst, const u32 *omeg
     }
     g_whole_last = slot;
     TwiddleCache &tw = g_twiddles[TW_WHOLE + slot];
+    wt.tw = &tw;
     PANDA_TRY(tw.settle(stream));
     const bool hit = tw.valid && tw.device == dev && memcmp(key, tw.key, sizeof(key)) == 0;
-    Fe<Fr> omega, scale;
+    Fe<Fr> &omega = wt.omega, &scale = wt.scale;
     fe_zero(omega);
     fe_zero(scale);
     if (!hit) { // host-side parameters (two Fermat inversions for the inverse transform) only when tables are rebuilt
@@ -1096,6 +1168,25 @@ hipError_t ntt_run(hipStream_t stream, void *d_src, void *d_dst, const u32 *omeg
     } else
         tw.used = 0;
     tw.valid = false;
+    wt.hit = hit;
+    wt.streamed = streamed;
+    return hipSuccess;
+}
+
+template <class Fr>
+hipError_t ntt_run(hipStream_t stream, void *d_src, void *d_dst, const u32 *omega_wire, unsigned log_n, unsigned *flag, bool inverse, bool br_in = false,
+                   bool br_out = false)
+{
+    if (log_n > 28 || !d_src || !d_dst || !omega_wire) return hipErrorInvalidValue;
+    if (panda::extent_too_short(d_src, (size_t)32 << log_n) || panda::extent_too_short(d_dst, (size_t)32 << log_n)) return hipErrorInvalidValue;
+    PANDA_TRY(order_after_null_stream(stream));
+    WholeTables<Fr> wt;
+    PANDA_TRY(whole_tables<Fr>(stream, omega_wire, log_n, inverse, br_in, br_out, wt));
+    TwiddleCache &tw = *wt.tw;
+    const bool hit = wt.hit;
+    const unsigned streamed = wt.streamed;
+    const u32(&key)[12] = wt.key;
+    const Fe<Fr> &omega = wt.omega, &scale = wt.scale;
     unsigned passes = 0;
     PassTimer &pt = g_pass_timer;
     // clock stamps around the passes (panda_set_clock_stamps; panda_internal.h): cycles and the clock they ran at, beside the milliseconds
@@ -1180,6 +1271,35 @@ bool batch_shape_invalid(unsigned kind, unsigned log_n, unsigned batch)
 // prover's round shifts every polynomial by the same generator
 thread_local TwiddleCache g_coset_tables;
 
+// The two-level power tables of an element-wise sweep over exponents below 2^log_n, in the cache entry `ct` under `key`: ta[j] = base^j,
+// j < min(n, 2^16); tb[j] = base^(2^16 j), j < n / 2^16; base = g, or g^-1 with `invert`.  Built on `stream` unless the entry holds them;
+// the entry is left invalid, and the caller publishes `key` once its stream has been waited for.
+template <class Fr>
+hipError_t power_tables(hipStream_t stream, TwiddleCache &ct, const u32 (&key)[12], int dev, const Fe<Fr> &g, bool invert, unsigned log_n, u32 **d_a, u32 **d_b)
+{
+    const bool chit = ct.valid && ct.device == dev && memcmp(key, ct.key, sizeof(key)) == 0;
+    if (!chit)
+        PANDA_TRY(ct.ensure(SZ_TA + SZ_TB + 4096));
+    else
+        ct.used = 0;
+    ct.valid = false;
+    *d_a = (u32 *)ct.take(SZ_TA);
+    *d_b = (u32 *)ct.take(SZ_TB);
+    if (!*d_a || !*d_b) return hipErrorOutOfMemory;
+    if (!chit) {
+        Fe<Fr> base = g;
+        if (invert) fe_inv(base, g);
+        build_table<Fr>(stream, base, nullptr, (unsigned)std::min<u64>((u64)1 << log_n, 1u << 16), *d_a);
+        if (log_n > 16) {
+            Fe<Fr> base_b;
+            fe_pow_u64(base_b, base, (u64)1 << 16);
+            build_table<Fr>(stream, base_b, nullptr, 1u << (log_n - 16), *d_b);
+        }
+        PANDA_TRY(hipGetLastError());
+    }
+    return hipSuccess;
+}
+
 // `batch` transforms of 2^log_n points, member j at element offset j 2^log_n of d_src / d_dst: one table set (the single call's, under the
 // single call's key), every pass launched once over all members, the coset kinds' shift as ONE sweep over the batch in front of
 // (forward) or behind (inverse) the passes, one synchronisation.  The caller has checked the shape and the pointers.
@@ -1198,72 +1318,21 @@ hipError_t ntt_run_batch(hipStream_t stream, void *d_src, void *d_dst, const u32
     const size_t bytes = ((size_t)batch << log_n) * 32;
     if (panda::extent_too_short(d_src, bytes) || panda::extent_too_short(d_dst, bytes)) return hipErrorInvalidValue;
     PANDA_TRY(order_after_null_stream(stream));
-    u32 key[12];
-    int dev = -1;
-    PANDA_TRY(hipGetDevice(&dev));
     // the whole-transform tables of ONE member, looked up and built exactly as ntt_run does
-    const unsigned mode = g_streamed_tables.load(std::memory_order_relaxed);
-    unsigned streamed = mode == STREAMED_FAIL_ALLOC ? STREAMED_POLICY : mode, streamed_bits = 0;
-    const PassPlan pl = plan_passes(log_n, br_in, br_out);
-    for (unsigned j = 0; j < pl.count; j++) streamed_bits = std::max(streamed_bits, streamed_table_bits(pl, j, log_n, streamed));
-    if (!streamed_bits || (g_streamed_unavailable.device == dev && streamed_bits >= g_streamed_unavailable.bits)) streamed = 0;
-    const unsigned variant = (inverse ? 1u : 0u) | (br_in ? 2u : 0u) | (br_out ? 4u : 0u);
-    twiddle_key<Fr>(key, log_n, variant | (streamed << 3), omega_wire);
-    unsigned slot = g_whole_last ^ 1u;
-    for (unsigned c = 0; c < 2; c++) {
-        const TwiddleCache &t = g_twiddles[TW_WHOLE + c];
-        if (t.valid && t.device == dev && memcmp(key, t.key, sizeof(key)) == 0) slot = c;
-    }
-    g_whole_last = slot;
-    TwiddleCache &tw = g_twiddles[TW_WHOLE + slot];
-    PANDA_TRY(tw.settle(stream));
-    const bool hit = tw.valid && tw.device == dev && memcmp(key, tw.key, sizeof(key)) == 0;
-    Fe<Fr> omega, scale;
-    fe_zero(omega);
-    fe_zero(scale);
-    if (!hit) {
-        fe_from_wire(omega, omega_wire);
-        if (inverse) inverse_parameters<Fr>(omega, scale, (u64)1 << log_n);
-        hipError_t got = (streamed && mode == STREAMED_FAIL_ALLOC) ? hipErrorOutOfMemory : tw.ensure(passes_table_bytes(log_n, br_in, br_out, streamed) + 4096);
-        if (got == hipErrorOutOfMemory && streamed) { // as ntt_run: this size runs with the two small tables from now on
-            (void)hipGetLastError();
-            if (g_streamed_unavailable.device != dev) g_streamed_unavailable = StreamedUnavailable{dev, streamed_bits};
-            g_streamed_unavailable.bits = std::min(g_streamed_unavailable.bits, streamed_bits);
-            streamed = 0;
-            twiddle_key<Fr>(key, log_n, variant, omega_wire);
-            got = tw.ensure(passes_table_bytes(log_n, br_in, br_out, 0) + 4096);
-        }
-        PANDA_TRY(got);
-        g_table_builds++;
-    } else
-        tw.used = 0;
-    tw.valid = false;
-    // the sweep's tables: ta[j] = g^j, j < min(n, 2^16); tb[j] = g^(2^16 j), j < n / 2^16
+    WholeTables<Fr> wt;
+    PANDA_TRY(whole_tables<Fr>(stream, omega_wire, log_n, inverse, br_in, br_out, wt));
+    TwiddleCache &tw = *wt.tw;
+    const bool hit = wt.hit;
+    const unsigned streamed = wt.streamed;
+    const int dev = wt.device;
+    const u32(&key)[12] = wt.key;
+    const Fe<Fr> &omega = wt.omega, &scale = wt.scale;
     TwiddleCache &ct = g_coset_tables;
     u32 ckey[12];
     u32 *d_ca = nullptr, *d_cb = nullptr;
     if (coset) {
         twiddle_key<Fr>(ckey, log_n, inverse ? 1u : 0u, shift_wire);
-        const bool chit = ct.valid && ct.device == dev && memcmp(ckey, ct.key, sizeof(ckey)) == 0;
-        if (!chit)
-            PANDA_TRY(ct.ensure(SZ_TA + SZ_TB + 4096));
-        else
-            ct.used = 0;
-        ct.valid = false;
-        d_ca = (u32 *)ct.take(SZ_TA);
-        d_cb = (u32 *)ct.take(SZ_TB);
-        if (!d_ca || !d_cb) return hipErrorOutOfMemory;
-        if (!chit) {
-            Fe<Fr> base = g;
-            if (inverse) fe_inv(base, g);
-            build_table<Fr>(stream, base, nullptr, (unsigned)std::min<u64>((u64)1 << log_n, 1u << 16), d_ca);
-            if (log_n > 16) {
-                Fe<Fr> base_b;
-                fe_pow_u64(base_b, base, (u64)1 << 16);
-                build_table<Fr>(stream, base_b, nullptr, 1u << (log_n - 16), d_cb);
-            }
-            PANDA_TRY(hipGetLastError());
-        }
+        PANDA_TRY(power_tables<Fr>(stream, ct, ckey, dev, g, inverse, log_n, &d_ca, &d_cb));
     }
     const unsigned count = batch << log_n, sweep_blocks = (count + 255) / 256;
     unsigned passes = 0;
@@ -1300,6 +1369,101 @@ hipError_t ntt_run_batch(hipStream_t stream, void *d_src, void *d_dst, const u32
         memcpy(ct.key, ckey, sizeof(ckey));
         ct.valid = true;
     }
+    return hipSuccess;
+}
+
+// ---- low-degree extension: coefficients to the evaluations on a coset of the 2^log_blowup times larger domain (panda_ntt_execute_lde)
+constexpr unsigned LDE_NATURAL = PANDA_NTT_LDE_NATURAL; // the other order, PANDA_NTT_LDE_COSET_MAJOR = 0, is what the passes leave
+static_assert(PANDA_NTT_LDE_COSET_MAJOR == 0 && LDE_NATURAL == 1, "the order counts the interleave's launch and flag flip");
+
+bool lde_shape_invalid(unsigned log_n, unsigned log_blowup, unsigned batch, unsigned order)
+{
+    if (order > LDE_NATURAL || log_blowup == 0 || log_blowup > PANDA_NTT_LDE_MAX_LOG_BLOWUP || log_n > 28 || batch == 0) return true;
+    return ((u64)batch << log_blowup) > PANDA_NTT_MAX_BATCH || ((u64)batch << (log_n + log_blowup)) > ((u64)1 << BATCH_MAX_LOG_ELEMS);
+}
+
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// power tables of the root of the extended domain for k_lde_expand, per host thread, keyed by field, size, blow-up and root
+thread_local TwiddleCache g_lde_tables;
+
+void launch_lde_interleave(unsigned log_b, const u32 *x, u32 *y, unsigned log_n, unsigned count, hipStream_t s)
+{
+    const dim3 grid((count + 255) / 256), block(256);
+    switch (log_b) {
+    case 1: hipLaunchKernelGGL(k_lde_interleave<1>, grid, block, 0, s, x, y, log_n, count); break;
+    case 2: hipLaunchKernelGGL(k_lde_interleave<2>, grid, block, 0, s, x, y, log_n, count); break;
+    case 3: hipLaunchKernelGGL(k_lde_interleave<3>, grid, block, 0, s, x, y, log_n, count); break;
+    default: hipLaunchKernelGGL(k_lde_interleave<4>, grid, block, 0, s, x, y, log_n, count); break;
+    }
+}
+
+// f(g w^(i + B k)), k < n, is the n-point transform with root w^B of c_j (g w^i)^j: the extension of `batch` polynomials is
+// k_lde_expand into d_src, the batch's passes over batch x B members under the single call's table key for (log_n, forward, w^B), and for
+// the NATURAL order k_lde_interleave into the other buffer.  The caller has checked the shape, the pointers and the overlap.
+template <class Fr>
+hipError_t ntt_run_lde(hipStream_t stream, const void *d_coeffs, void *d_src, void *d_dst, const u32 *omega_wire, unsigned log_n, unsigned *flag,
+                       unsigned log_blowup, unsigned batch, const u32 *shift_wire, unsigned order)
+{
+    Fe<Fr> g, w;
+    fe_from_wire(g, shift_wire);
+    if (fe_is_zero_mod_p(g)) return hipErrorInvalidValue;
+    const size_t cbytes = ((size_t)batch << log_n) * 32, bytes = cbytes << log_blowup;
+    if (panda::extent_too_short(d_coeffs, cbytes) || panda::extent_too_short(d_src, bytes) || panda::extent_too_short(d_dst, bytes)) return hipErrorInvalidValue;
+    // the members' root w^B, in the form the single call of 2^log_n points would be handed it
+    fe_from_wire(w, omega_wire);
+    Fe<Fr> wn = w;
+    for (unsigned i = 0; i < log_blowup; i++) fe_sqr(wn, wn);
+    u32 member_omega[8];
+    fe_to_wire(member_omega, wn);
+    PANDA_TRY(order_after_null_stream(stream));
+    WholeTables<Fr> wt;
+    PANDA_TRY(whole_tables<Fr>(stream, member_omega, log_n, false, false, false, wt));
+    TwiddleCache &tw = *wt.tw;
+    u32 gkey[12], wkey[12];
+    u32 *d_ga = nullptr, *d_gb = nullptr, *d_wa = nullptr, *d_wb = nullptr;
+    twiddle_key<Fr>(gkey, log_n, 0, shift_wire); // the key of a forward coset batch of this size and shift: the same tables
+    PANDA_TRY(power_tables<Fr>(stream, g_coset_tables, gkey, wt.device, g, false, log_n, &d_ga, &d_gb));
+    twiddle_key<Fr>(wkey, log_n, log_blowup, omega_wire);
+    PANDA_TRY(power_tables<Fr>(stream, g_lde_tables, wkey, wt.device, w, false, log_n, &d_wa, &d_wb));
+    const unsigned members = batch << log_blowup, count = batch << log_n, blocks = (count + 255) / 256;
+    unsigned passes = 0;
+    PassTimer &pt = g_pass_timer;
+    const bool stamps = panda::clock_stamps_enabled();
+    uint64_t *stamp_block = nullptr;
+    panda::thread_ntt_clock() = panda::ClockDelta{};
+    if (stamps) {
+        PANDA_TRY(panda::thread_stamp_blocks(&stamp_block));
+        stamp_block += 2 * 2 * panda::CLOCK_STAMP_SLOTS;
+        for (unsigned i = 0; i < 2 * 2 * panda::CLOCK_STAMP_SLOTS; i++) stamp_block[i] = 0;
+    }
+    hipLaunchKernelGGL(k_lde_expand<Fr>, dim3(blocks), dim3(256), 0, stream, (const u32 *)d_coeffs, (u32 *)d_src, d_ga, d_gb, d_wa, d_wb, log_n, log_blowup, count);
+    PANDA_TRY(hipGetLastError());
+    PANDA_TRY(pt.begin(stream));
+    if (stamps) PANDA_TRY(panda::enqueue_clock_stamp(stream, stamp_block));
+    PANDA_TRY(ntt_passes<Fr>(stream, tw, (const u32 *)d_src, (u32 *)d_dst, wt.omega, log_n, (const Fe<Fr> *)nullptr, &passes, !wt.hit, false, false, wt.streamed, members));
+    if (stamps) PANDA_TRY(panda::enqueue_clock_stamp(stream, stamp_block + 2 * panda::CLOCK_STAMP_SLOTS));
+    PANDA_TRY(pt.end(stream));
+    if (order == LDE_NATURAL) {
+        const bool in_dst = passes & 1u;
+        launch_lde_interleave(log_blowup, in_dst ? (const u32 *)d_dst : (const u32 *)d_src, in_dst ? (u32 *)d_src : (u32 *)d_dst, log_n, count, stream);
+        PANDA_TRY(hipGetLastError());
+    }
+    *flag = (passes + order) & 1u;
+    PANDA_TRY(hipStreamSynchronize(stream));
+    pt.read();
+    if (stamps) panda::thread_ntt_clock() = panda::clock_delta(stamp_block, stamp_block + 2 * panda::CLOCK_STAMP_SLOTS);
+    memcpy(tw.key, wt.key, sizeof(wt.key));
+    tw.valid = true; // only after the tables are known to be complete
+    tw.has_pending = false;
+    memcpy(g_coset_tables.key, gkey, sizeof(gkey));
+    g_coset_tables.valid = true;
+    memcpy(g_lde_tables.key, wkey, sizeof(wkey));
+    g_lde_tables.valid = true;
     return hipSuccess;
 }
 
@@ -1691,6 +1855,33 @@ panda_error panda_ntt_batch_plan(unsigned log_n, unsigned kind, unsigned batch, 
     return panda_success;
 }
 
+// Low-degree extension: see include/panda_interface.h.  The shape, pointer and overlap checks come before any runtime call.
+panda_error panda_ntt_execute_lde(unsigned field, const panda_ntt_configuration_v1 cfg, const void *d_coeffs, unsigned log_blowup, unsigned batch, const void *shift,
+                                  unsigned order)
+{
+    if (field > 2 || lde_shape_invalid(cfg.log_n, log_blowup, batch, order)) return panda_error_invalid_value;
+    if (!d_coeffs || !cfg.d_src || !cfg.d_dst || !cfg.d_omega || !cfg.flag || !shift) return panda_error_invalid_value;
+    const size_t cbytes = ((size_t)batch << cfg.log_n) * 32, bytes = cbytes << log_blowup;
+    if (ranges_overlap(d_coeffs, cbytes, cfg.d_src, bytes) || ranges_overlap(d_coeffs, cbytes, cfg.d_dst, bytes)) return panda_error_invalid_value;
+    hipStream_t stream = static_cast<hipStream_t>(cfg.stream.handle);
+    const u32 *omega = (const u32 *)cfg.d_omega, *g = (const u32 *)shift;
+    unsigned *flag = (unsigned *)cfg.flag;
+    switch (field) {
+    case 0: return static_cast<panda_error>(ntt_run_lde<Bn254Fr>(stream, d_coeffs, cfg.d_src, cfg.d_dst, omega, cfg.log_n, flag, log_blowup, batch, g, order));
+    case 1: return static_cast<panda_error>(ntt_run_lde<Bls377Fr>(stream, d_coeffs, cfg.d_src, cfg.d_dst, omega, cfg.log_n, flag, log_blowup, batch, g, order));
+    default: return static_cast<panda_error>(ntt_run_lde<Bls381Fr>(stream, d_coeffs, cfg.d_src, cfg.d_dst, omega, cfg.log_n, flag, log_blowup, batch, g, order));
+    }
+}
+
+panda_error panda_ntt_lde_plan(unsigned log_n, unsigned log_blowup, unsigned batch, unsigned order, unsigned *launches, unsigned *flag)
+{
+    if (lde_shape_invalid(log_n, log_blowup, batch, order)) return panda_error_invalid_value;
+    const unsigned passes = plan_passes(log_n).count;
+    if (launches) *launches = 1 + passes + order;
+    if (flag) *flag = (passes + order) & 1u;
+    return panda_success;
+}
+
 panda_error panda_ntt_last_clock(uint64_t *out)
 {
     if (!out) return panda_error_invalid_value;
@@ -1738,6 +1929,7 @@ panda_error panda_ntt_tear_down(void)
     g_streamed_unavailable = StreamedUnavailable{};
     for (auto &t : g_twiddles) (void)t.release();
     (void)g_coset_tables.release();
+    (void)g_lde_tables.release();
     return static_cast<panda_error>(panda::release_thread_arena());
 }
 

@@ -547,3 +547,43 @@ def panda_ntt_gpu_batch(gm: PandaGpuManager, polys, omega, log_n: int, field: in
             if d:
                 lib.panda_free(d)
     return flag.value
+
+
+def panda_ntt_gpu_lde(gm: PandaGpuManager, polys, omega_N, log_n: int, log_blowup: int, shift, field: int = 0, order: int = 0):
+    """Additive: the low-degree extension of equal-length coefficient arrays of 2^log_n elements (field 0 BN254 Fr, 1 BLS12-377 Fr,
+    2 BLS12-381 Fr) to the coset shift * H of the 2^log_blowup times larger domain with root `omega_N`, in ONE library call
+    (panda_ntt_execute_lde).  The host arrays are staged into one device buffer, polynomial after polynomial, and are not changed.
+    Returns a list of 2^(log_n + log_blowup)-element arrays (uint32, 8 words per element) in `order` (ffi.NTT_LDE_COSET_MAJOR: the
+    2^log_blowup cosets of the small domain one after the other; ffi.NTT_LDE_NATURAL: the order of a coset transform of the padded
+    polynomial); an empty list returns an empty list without a call."""
+    bufs = [_as_bytes(p) for p in polys]
+    if not bufs:
+        return []
+    size = (1 << log_n) * FIELD_ELEMENT_LEN
+    if any(b.size != size for b in bufs):
+        raise PandaGpuError("SchedulingErr")
+    lib = ffi.load()
+    o, g = _as_bytes(omega_N), _as_bytes(shift)
+    big = size << log_blowup
+    d_coeffs, d_src, d_dst = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    flag = C.c_uint(0)
+    out = []
+    try:
+        ffi.check(lib.panda_malloc(C.byref(d_coeffs), len(bufs) * size), "AsyncPoolMallocErr")
+        ffi.check(lib.panda_malloc(C.byref(d_src), len(bufs) * big), "AsyncPoolMallocErr")
+        ffi.check(lib.panda_malloc(C.byref(d_dst), len(bufs) * big), "AsyncPoolMallocErr")
+        for k, b in enumerate(bufs):
+            ffi.check(lib.panda_memcpy_async(C.c_void_p(d_coeffs.value + k * size), _ptr(b), size, gm.h2d_stream.raw), "AsyncMemcopyErr")
+        gm.wait_h2d()
+        cfg = ffi.NttconfigurationV1(gm.mem_pool, gm.exec_stream.raw, d_src, d_dst, _ptr(o), log_n, C.pointer(flag))
+        ffi.check(lib.panda_ntt_execute_lde(field, cfg, d_coeffs, log_blowup, len(bufs), _ptr(g), order), "SchedulingErr")
+        res = d_src.value if flag.value == 0 else d_dst.value
+        for k in range(len(bufs)):
+            ext = np.empty(big, np.uint8)
+            ffi.check(lib.panda_memcpy(_ptr(ext), C.c_void_p(res + k * big), big), "CreateContextError")
+            out.append(ext.view(np.uint32).reshape(-1, 8))
+    finally:
+        for d in (d_coeffs, d_src, d_dst):
+            if d:
+                lib.panda_free(d)
+    return out
