@@ -17,6 +17,7 @@
 
 #include "fe29.h"
 #include "msm_sort.h"
+#include "xcd_remap.h"
 
 using namespace panda29;
 
@@ -238,27 +239,97 @@ __global__ void __launch_bounds__(256) k_part_hist(const Code *__restrict__ dig,
     for (unsigned i = tid; i < g.H; i += 256) out[i] = h[i];
 }
 
-// tile_hist -> exclusive prefix over tiles (tile_pref), one WAVE per (window, partition) column: 64 tiles per step with a
-// shuffle scan instead of one dependent load per tile; column totals go to `totals`.  tile_hist keeps the counts: the
-// scatter kernels start from them instead of counting their tile again.
+// ---- the column scans: tile_hist -> exclusive prefix over tiles (tile_pref) and column totals -------------------------------------------
+// tile_hist keeps the counts: the scatter kernels start from them instead of counting their tile again.
+// A wave takes SIXTEEN columns and sixteen tiles per step: lane = 4 * (tile of the step) + (quad of columns), and every lane reads the 16
+// bytes of its four columns -- four lanes to a 64-byte sector, every byte of which is used.  (One column per wave and one tile per lane
+// read 4 bytes of every sector it touched: 0.2 TB/s.)  The scan over the tiles is a shuffle scan over the lanes 4 apart.
+
+// the four counts at row[c .. c + 3] (c a multiple of 4; columns from H on read as 0); vec: H is a multiple of 4, so rows start on 16 bytes
+__device__ __forceinline__ void load_cols4(u32 *v, const u32 *__restrict__ row, unsigned c, unsigned H, bool vec)
+{
+    if (vec) {
+        const uint4 q = c < H ? *reinterpret_cast<const uint4 *>(row + c) : uint4{0, 0, 0, 0};
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+    } else {
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) v[i] = c + i < H ? row[c + i] : 0;
+    }
+}
+__device__ __forceinline__ void store_cols4(u32 *__restrict__ row, const u32 *v, unsigned c, unsigned H, bool vec)
+{
+    if (vec) {
+        if (c < H) *reinterpret_cast<uint4 *>(row + c) = uint4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++)
+            if (c + i < H) row[c + i] = v[i];
+    }
+}
+// inclusive scan of v[0..3] over the sixteen tiles of a step (lanes 4 apart)
+__device__ __forceinline__ void scan_tiles16(u32 *v, unsigned lane)
+{
+#pragma unroll
+    for (unsigned d = 4; d < 64; d <<= 1) {
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) {
+            const u32 up = __shfl_up(v[i], d, 64);
+            if (lane >= d) v[i] += up;
+        }
+    }
+}
+
+// Level 1: workgroup (sixteen columns, window).  Its sixteen waves share the tiles out in contiguous shares: a wave first adds its share
+// up (independent loads), the shares' totals meet in LDS, then every wave scans its share again (from L2) from where the waves before
+// it end.  Column totals go to `totals`.
 __global__ void __launch_bounds__(1024) k_part_scan_cols(const u32 *__restrict__ tile_hist, u32 *__restrict__ tile_pref, u32 *__restrict__ totals, SortGeom g)
 {
-    const unsigned w = blockIdx.y, lane = threadIdx.x & 63, h = blockIdx.x * 16 + (threadIdx.x >> 6);
-    if (h >= g.H) return; // whole wave exits together
-    const u64 col = (u64)w * g.tiles * g.H + h;
-    u32 run = 0;
-    for (unsigned t0 = 0; t0 < g.tiles; t0 += 64) {
-        const unsigned tile = t0 + lane;
-        u32 v = tile < g.tiles ? tile_hist[col + (u64)tile * g.H] : 0;
-        u32 inc = v;
-        for (unsigned d = 1; d < 64; d <<= 1) {
-            u32 up = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += up;
+    __shared__ u32 wtot[16][16];
+    const unsigned w = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ts = lane >> 2, quad = lane & 3u;
+    const unsigned c = blockIdx.x * 16 + 4 * quad;
+    const bool vec = !(g.H & 3u);
+    const u64 base = (u64)w * g.tiles * g.H;
+    const unsigned per = (g.tiles + 255) / 256 * 16; // tiles per wave: whole steps
+    const unsigned t_lo = min(wave * per, g.tiles), t_hi = min(t_lo + per, g.tiles);
+    u32 run[4] = {0, 0, 0, 0}, v[4];
+    for (unsigned t0 = t_lo; t0 < t_hi; t0 += 16) {
+        const unsigned tile = t0 + ts;
+        if (tile < t_hi) {
+            load_cols4(v, tile_hist + base + (u64)tile * g.H, c, g.H, vec);
+#pragma unroll
+            for (unsigned i = 0; i < 4; i++) run[i] += v[i];
         }
-        if (tile < g.tiles) tile_pref[col + (u64)tile * g.H] = run + inc - v;
-        run += __shfl(inc, 63, 64);
     }
-    if (lane == 0) totals[(u64)w * g.H + h] = run;
+#pragma unroll
+    for (unsigned d = 4; d < 64; d <<= 1)
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) run[i] += __shfl_xor(run[i], d, 64);
+    if (ts == 0)
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) wtot[wave][4 * quad + i] = run[i];
+    __syncthreads();
+#pragma unroll
+    for (unsigned i = 0; i < 4; i++) {
+        run[i] = 0;
+        for (unsigned j = 0; j < wave; j++) run[i] += wtot[j][4 * quad + i];
+    }
+    for (unsigned t0 = t_lo; t0 < t_hi; t0 += 16) {
+        const unsigned tile = t0 + ts;
+        u32 inc[4] = {0, 0, 0, 0};
+        if (tile < t_hi) load_cols4(inc, tile_hist + base + (u64)tile * g.H, c, g.H, vec);
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) v[i] = inc[i];
+        scan_tiles16(inc, lane);
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) v[i] = run[i] + inc[i] - v[i];
+        if (tile < t_hi) store_cols4(tile_pref + base + (u64)tile * g.H, v, c, g.H, vec);
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) run[i] += __shfl(inc[i], 60 + quad, 64);
+    }
+    if (wave == 15 && ts == 0) // the last wave ends at the column's total (an empty share included)
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++)
+            if (c + i < g.H) totals[(u64)w * g.H + c + i] = run[i];
 }
 
 // inclusive scan over the workgroup of one value per thread: shuffles inside a wave, the wave totals through `wsum` (one LDS word per
@@ -355,7 +426,7 @@ __global__ void __launch_bounds__(SORT_THREADS) k_part_scatter(const Code *__res
     __shared__ Word words[SORT_TILE];
     __shared__ uint16_t parts_of[SORT_TILE];
     __shared__ u32 wsum[SORT_THREADS / 64];
-    const unsigned w = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const unsigned w = blockIdx.y, tile = panda::xcd_remap(blockIdx.x, gridDim.x), tid = threadIdx.x; // neighbouring tiles of a window on one XCD (xcd_remap.h)
     const u64 row = ((u64)w * g.tiles + tile) * g.H;
     const u32 *po = part_off + (u64)w * (g.H + 1);
     const u64 n = (u64)1 << g.log_n;
@@ -403,7 +474,7 @@ __global__ void __launch_bounds__(SORT_THREADS) k1_scatter_split(const Code *__r
     __shared__ u32 words[SORT_TILE];
     __shared__ u32 meta[SORT_TILE]; // partition << 8 | the b2 key bits
     __shared__ u32 wsum[SORT_THREADS / 64];
-    const unsigned w = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+    const unsigned w = blockIdx.y, tile = panda::xcd_remap(blockIdx.x, gridDim.x), tid = threadIdx.x, lane = tid & 63u; // as in k_part_scatter
     const u64 row = ((u64)w * g.tiles + tile) * g.H;
     const u32 *po = part_off + (u64)w * (g.H + 1);
     const u64 n = (u64)1 << g.log_n;
@@ -627,46 +698,62 @@ __global__ void __launch_bounds__(256) k2_hist(const unsigned char *__restrict__
     unsigned tile;
     TileRange r;
     if (!locate_tile(r, tile, blockIdx.x, seg_tile, part_off, g, R)) return;
-    h[tid] = 0;
-    __syncthreads();
-    // 16 entries per load: aligned 16-byte vectors from the vector that contains `begin` on; bytes outside the tile are
-    // skipped by index (the array is padded by 16 bytes, so the last vector may run past `end`)
-    const u64 first = r.begin & ~(u64)15;
-    for (u64 a = first + (u64)tid * 16; a < r.end; a += 256 * 16) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(p1_hi + a);
+    // 16 entries per load: aligned 16-byte vectors from the vector that contains `begin` on; bytes outside the tile count as 0
+    // (the array is padded by 16 bytes, so the last vector may run past `end`).  A tile is two vectors per thread, and one more for
+    // thread 0 where it does not start on 16 bytes: both go out before the counters are cleared, and the sixteen LDS atomics of a vector
+    // follow each other without a branch or a wait between them.
+    const u64 first = r.begin & ~(u64)15, a0 = first + (u64)tid * 16;
+    auto count = [&](const uint4 &v, u64 a) {
         const u32 wv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int j = 0; j < 16; j++) {
             const u64 i = a + j;
-            if (i >= r.begin && i < r.end) atomicAdd(&h[(wv[j >> 2] >> (8 * (j & 3))) & 0xffu], 1u);
+            atomicAdd(&h[(wv[j >> 2] >> (8 * (j & 3))) & 0xffu], (i >= r.begin && i < r.end) ? 1u : 0u);
         }
-    }
+    };
+    uint4 v0{0, 0, 0, 0}, v1{0, 0, 0, 0};
+    if (a0 < r.end) v0 = *reinterpret_cast<const uint4 *>(p1_hi + a0);
+    if (a0 + 256 * 16 < r.end) v1 = *reinterpret_cast<const uint4 *>(p1_hi + a0 + 256 * 16);
+    h[tid] = 0;
+    __syncthreads();
+    if (a0 < r.end) count(v0, a0);
+    if (a0 + 256 * 16 < r.end) count(v1, a0 + 256 * 16);
+    for (u64 a = a0 + 2 * 256 * 16; a < r.end; a += 256 * 16) count(*reinterpret_cast<const uint4 *>(p1_hi + a), a);
     __syncthreads();
     if (tid < g.H2) tile_hist[(u64)tile * g.H2 + tid] = h[tid];
 }
 
-// one WAVE per (segment, h2) column: exclusive prefix over the segment's tiles (tile_pref), column total to totals[s][h2]
+// Level 2: a wave per (segment, sixteen h2 columns): exclusive prefix over the segment's tiles (tile_pref), column totals to totals[s][h2].
+// A segment of uniform scalars has a step or two of tiles; the next step's counts are loaded under the scan of this one's.
 __global__ void __launch_bounds__(256) k2_scan_cols(const u32 *__restrict__ tile_hist, u32 *__restrict__ tile_pref, const u32 *__restrict__ seg_tile,
                                                     u32 *__restrict__ totals, TabledGeom g, SortRange R)
 {
     __builtin_amdgcn_s_setprio(3); // beside the bucket accumulation of a split sort (SortSplit) these waves must win the issue arbitration: they issue little, it issues always
-    // four waves, four columns (a wave per SIMD: sixteen-wave workgroups of this kernel took 3.9 ms beside the accumulation, 0.03 alone)
-    const unsigned s = R.s_lo + blockIdx.y, lane = threadIdx.x & 63, h = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (h >= g.H2) return; // whole wave exits together
+    // four waves, 64 columns (a wave per SIMD: sixteen-wave workgroups of this kernel took 3.9 ms beside the accumulation, 0.03 alone)
+    const unsigned s = R.s_lo + blockIdx.y, lane = threadIdx.x & 63, ts = lane >> 2, quad = lane & 3u;
+    const unsigned c0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16, c = c0 + 4 * quad;
+    if (c0 >= g.H2) return; // whole wave exits together
+    const bool vec = !(g.H2 & 3u);
     const unsigned t_begin = seg_tile[s], t_end = seg_tile[s + 1];
-    u32 run = 0;
-    for (unsigned t0 = t_begin; t0 < t_end; t0 += 64) {
-        const unsigned tile = t0 + lane;
-        u32 v = tile < t_end ? tile_hist[(u64)tile * g.H2 + h] : 0;
-        u32 inc = v;
-        for (unsigned d = 1; d < 64; d <<= 1) {
-            u32 up = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += up;
-        }
-        if (tile < t_end) tile_pref[(u64)tile * g.H2 + h] = run + inc - v;
-        run += __shfl(inc, 63, 64);
+    u32 run[4] = {0, 0, 0, 0}, next[4] = {0, 0, 0, 0};
+    if (t_begin + ts < t_end) load_cols4(next, tile_hist + (u64)(t_begin + ts) * g.H2, c, g.H2, vec);
+    for (unsigned t0 = t_begin; t0 < t_end; t0 += 16) {
+        const unsigned tile = t0 + ts;
+        u32 v[4], inc[4];
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) v[i] = inc[i] = next[i], next[i] = 0;
+        if (tile + 16 < t_end) load_cols4(next, tile_hist + (u64)(tile + 16) * g.H2, c, g.H2, vec);
+        scan_tiles16(inc, lane);
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) v[i] = run[i] + inc[i] - v[i];
+        if (tile < t_end) store_cols4(tile_pref + (u64)tile * g.H2, v, c, g.H2, vec);
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) run[i] += __shfl(inc[i], 60 + quad, 64);
     }
-    if (lane == 0) totals[(u64)s * g.H2 + h] = run;
+    if (ts == 0)
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++)
+            if (c + i < g.H2) totals[(u64)s * g.H2 + c + i] = run[i];
 }
 
 // one block per segment: sub_off[s][0..H2] = exclusive scan of the column totals (relative to the segment start)
@@ -699,7 +786,11 @@ __global__ void __launch_bounds__(THREADS) k2_scatter(const u32 *__restrict__ p1
     const unsigned tid = threadIdx.x;
     unsigned tile;
     TileRange r;
-    if (!locate_tile(r, tile, blockIdx.x, seg_tile, part_off, g, R)) return;
+    // the launch covers an upper bound of tiles; the ones the range has are dealt out so that an XCD's workgroups take neighbouring tiles
+    // (xcd_remap.h: a tile's run of a sub-partition ends where the next tile's begins)
+    const unsigned ntiles = seg_tile[R.s_hi] - seg_tile[R.s_lo];
+    if (blockIdx.x >= ntiles) return;
+    if (!locate_tile(r, tile, panda::xcd_remap(blockIdx.x, ntiles), seg_tile, part_off, g, R)) return;
     // 8 entries per thread and step: one aligned 8-byte vector of keys and the two 16-byte vectors of words that go with it (both arrays
     // are padded, entries outside the tile are skipped by index).  With 1024 threads that is the whole tile in one step (and one more
     // vector for thread 0 where the tile does not start on 8 entries); the loads of the first step go out before the counts are read and
@@ -1388,7 +1479,7 @@ static hipError_t sort3(hipStream_t stream, Arena &arena, unsigned fr, const voi
     // workgroups beyond the range's last tile leave after two loads.
     auto level2 = [&](hipStream_t s, const SortRange &R) {
         hipLaunchKernelGGL(k2_hist, dim3(g.max_tiles2), dim3(256), 0, s, d_p1_hi, d_poff, d_segtile, d_thist2, g, R);
-        hipLaunchKernelGGL(k2_scan_cols, dim3((g.H2 + 3) / 4, R.s_hi - R.s_lo), dim3(256), 0, s, d_thist2, d_tpref2, d_segtile, d_tot2, g, R);
+        hipLaunchKernelGGL(k2_scan_cols, dim3((g.H2 + 63) / 64, R.s_hi - R.s_lo), dim3(256), 0, s, d_thist2, d_tpref2, d_segtile, d_tot2, g, R);
         hipLaunchKernelGGL(k2_offsets, dim3(R.s_hi - R.s_lo), dim3(256), 0, s, d_tot2, d_suboff, g, R);
         if (s == stream)
             hipLaunchKernelGGL(k2_scatter<SORT_THREADS>, dim3(g.max_tiles2), dim3(SORT_THREADS), 0, s, d_p1_lo, d_p1_hi, d_poff, d_segtile, d_thist2, d_tpref2, d_suboff, d_p2, g, R);
