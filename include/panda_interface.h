@@ -12,8 +12,8 @@
  *
  * Part 2 are the four symbols the Rust side declares but the reference never defines
  * (binding.rs:14,16,54-56).  Part 3 is additive (no reference counterpart): BLS12-377 / BLS12-381 / BN254 G2 / BLS12-381 G2 / BLS12-377 G2,
- * cached-base registration and tables, the in-call upload pipeline, inverse / coset / bit-reversed NTTs, multi-GPU halves and
- * synthetic-input / diagnostics entry points.
+ * cached-base registration and tables, the in-call upload pipeline, inverse / coset / bit-reversed NTTs, batches, the low-degree
+ * extension, polynomial evaluation and division by X - z, multi-GPU halves and synthetic-input / diagnostics entry points.
  *
  * Conventions (unchanged from the reference):
  *   - return value: the HIP runtime's error code cast to unsigned; 0 = success
@@ -364,6 +364,35 @@ panda_error panda_ntt_execute_lde(unsigned field, const panda_ntt_configuration_
  * NATURAL order's interleave; *flag = the value panda_ntt_execute_lde will write, (passes + order) & 1.  Neither depends on `batch`.
  * Either pointer may be NULL.  Invalid for the shapes panda_ntt_execute_lde refuses. */
 panda_error panda_ntt_lde_plan(unsigned log_n, unsigned log_blowup, unsigned batch, unsigned order, unsigned *launches, unsigned *flag);
+/* KZG openings: evaluation of `batch` polynomials at a few points, and their division by X - z -- what a prover does with the coefficients
+ * an inverse transform left on the device, between that transform and the MSM that commits to the opening quotient.  With the suffix
+ * Horner values S_j = sum_{i >= j} c_i z^(i-j) (S_j = c_j + z S_(j+1), S_n = 0): f(z) = S_0, and (f(X) - f(z)) / (X - z) has the
+ * coefficients q_j = S_(j+1), j < n - 1; q_(n-1) = 0 is written as well, so the quotient has n elements and is ready for an MSM of the
+ * same size (panda_msm_execute_* take it as their scalars as it stands).
+ *   field: 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr.  Elements are 32-byte little-endian Montgomery-form residues; polynomial p starts at
+ *     byte p x n x 32 of d_coeffs and of d_quot.  n is ANY count from 1 up, not a power of two (blinded polynomials have 2^k + 2 or 2^k + 3
+ *     coefficients).  batch >= 1, batch x n <= 2^28.
+ *   points / point: HOST pointers (n_points x 32 B / 32 B), like d_omega and shift; a point's 256-bit value must be below the modulus.
+ *   values (HOST, batch x n_points x 32 B): f_p(z_k) at element p x n_points + k.  remainders (HOST, batch x 32 B, may be NULL): f_p(z).
+ *   Outputs are canonical.  Both calls are synchronous on return and read d_coeffs only; d_quot == d_coeffs exactly (division in place) is
+ *     legal.  Bytes behind the `batch` polynomials of either buffer are never written.
+ *   Division is three kernel launches (tile totals; one workgroup per polynomial over the totals; apply), evaluation the first two, once
+ *     per point; no kernel waits for another workgroup.  The scratch (32 bytes per tile and per value) is the calling host thread's arena: a
+ *     repeated call of the same shape allocates nothing, panda_ntt_tear_down releases it.
+ *   panda_error_invalid_value, nothing launched, no output written: field > 2, n == 0, batch == 0, batch x n > 2^28, n_points == 0 or >
+ *     PANDA_POLY_MAX_POINTS, a NULL buffer or point other than remainders, a point >= the modulus, d_quot and d_coeffs overlapping as
+ *     address ranges without being equal (all checked before any runtime call), and buffers of this library's allocators shorter than
+ *     stated. */
+#define PANDA_POLY_MAX_POINTS 8
+panda_error panda_poly_evaluate(unsigned field, const void *d_coeffs, uint64_t n, unsigned batch, const void *points /* HOST, n_points x 32 B */, unsigned n_points,
+                                void *values /* HOST, batch x n_points x 32 B */, panda_stream stream);
+panda_error panda_poly_divide_linear(unsigned field, const void *d_coeffs, void *d_quot, uint64_t n, unsigned batch, const void *point /* HOST, 32 B */,
+                                     void *remainders /* HOST, batch x 32 B, may be NULL */, panda_stream stream);
+/* How the two calls run (pure host arithmetic, no device call): *tile = the coefficients one workgroup covers, *carry_chunk = the tile
+ * totals the second level combines per step, *launches_evaluate = the kernel launches of one sweep over the coefficients (one sweep per
+ * point), *launches_divide = those of a division.  None depends on `batch`.  Any pointer may be NULL.  Invalid for the shapes the execute
+ * calls refuse (n == 0, batch == 0, batch x n > 2^28). */
+panda_error panda_poly_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *carry_chunk, unsigned *launches_evaluate, unsigned *launches_divide);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

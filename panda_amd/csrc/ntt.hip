@@ -1658,6 +1658,10 @@ hipError_t slab_inverse_local(const panda_ntt_slab_configuration &cfg, bool wait
 
 } // namespace
 
+namespace panda {
+hipError_t order_after_null_stream(hipStream_t stream) { return ::order_after_null_stream(stream); }
+} // namespace panda
+
 extern "C" {
 
 panda_error panda_ntt_setup_bn254(void *input_omega)

@@ -54,6 +54,9 @@ hipError_t release_thread_arena();
 // a second stream of this host thread on the current device (created on first use, destroyed with the arena): the other lane of an
 // MSM that runs in point ranges
 hipError_t thread_helper_stream(hipStream_t *out);
+// work enqueued on `stream` from here on runs behind what the NULL stream holds now (ntt.hip; a caller's panda_memset / panda_memcpy of
+// its buffers precedes a call on a non-blocking stream)
+hipError_t order_after_null_stream(hipStream_t stream);
 
 // Pinned host memory of this host thread that kernels write into directly (the stale-registration flag, the window sums or the
 // finished result of an MSM): what a call hands back to its host side arrives with the kernel that produced it, without a

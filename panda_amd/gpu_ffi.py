@@ -64,6 +64,7 @@ NTT_FORWARD, NTT_INVERSE, NTT_BITREV_OUT, NTT_INVERSE_BITREV_IN, NTT_COSET, NTT_
 # `order` of panda_ntt_execute_lde (PANDA_NTT_LDE_COSET_MAJOR, PANDA_NTT_LDE_NATURAL) and its largest log2 of the blow-up
 NTT_LDE_COSET_MAJOR, NTT_LDE_NATURAL = 0, 1
 NTT_LDE_MAX_LOG_BLOWUP = 4  # PANDA_NTT_LDE_MAX_LOG_BLOWUP
+POLY_MAX_POINTS = 8  # PANDA_POLY_MAX_POINTS
 CLOCK_WORDS, CLOCK_STAMP_BYTES = 12, 32768  # PANDA_CLOCK_WORDS, PANDA_CLOCK_STAMP_BYTES
 
 
@@ -104,6 +105,7 @@ ADDITIVE_SYMBOLS = [
     "panda_msm_execute_bls12_377_g2_multi", "panda_msm_execute_bls12_377_g2_from_host_multi",
     "panda_ntt_execute_batch", "panda_ntt_batch_plan",
     "panda_ntt_execute_lde", "panda_ntt_lde_plan",
+    "panda_poly_evaluate", "panda_poly_divide_linear", "panda_poly_plan",
 ]
 ALL_SYMBOLS = REFERENCE_SYMBOLS + RUST_ONLY_SYMBOLS + ADDITIVE_SYMBOLS
 
@@ -146,6 +148,8 @@ def load() -> C.CDLL:
         "panda_msm_execute_batch": [u, MSMConfiguration, u], "panda_msm_batch_plan": [u, u, u, u, C.POINTER(u), C.POINTER(u)],
         "panda_ntt_execute_batch": [u, u, NttconfigurationV1, u, vp], "panda_ntt_batch_plan": [u, u, u, C.POINTER(u), C.POINTER(u)],
         "panda_ntt_execute_lde": [u, NttconfigurationV1, vp, u, u, vp, u], "panda_ntt_lde_plan": [u, u, u, u, C.POINTER(u), C.POINTER(u)],
+        "panda_poly_evaluate": [u, vp, C.c_uint64, u, vp, u, vp, PandaStream], "panda_poly_divide_linear": [u, vp, vp, C.c_uint64, u, vp, vp, PandaStream],
+        "panda_poly_plan": [C.c_uint64, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)],
         "panda_msm_register_bases": [u, vp, u, PandaStream], "panda_msm_unregister_bases": [vp], "panda_msm_precompute_bases": [u, vp, u, u, PandaStream],
         "panda_msm_registered_info": [vp, C.POINTER(u), C.POINTER(u), C.POINTER(sz)], "panda_msm_set_chunk_entries": [u], "panda_msm_set_overlap": [u, u], "panda_msm_set_accumulate_variant": [u], "panda_msm_set_wide_merge": [u], "panda_msm_set_reduce_group": [u], "panda_msm_plain_window_plan": [u, u, C.POINTER(u), C.POINTER(u)], "panda_msm_verify_registered": [vp, PandaStream], "panda_msm_set_paranoid": [u], "panda_msm_set_phase_timing": [u], "panda_msm_setup_bls12_377": [], "panda_msm_execute_bls12_377": [MSMConfiguration], "panda_msm_execute_bls12_377_host": [MSMConfiguration],
         "panda_msm_set_window_bits": [u], "panda_msm_last_phase_ms": [C.POINTER(C.c_float)], "panda_ntt_last_device_ms": [C.POINTER(C.c_float)], "panda_ntt_pass_plan": [u, C.POINTER(C.c_uint), C.POINTER(C.c_uint)], "panda_ntt_set_streamed_tables": [u], "panda_ntt_execute_bn254_inverse": [NttconfigurationV1], "panda_ntt_execute_bls12_377_v1": [NttconfigurationV1], "panda_ntt_execute_bls12_377_inverse": [NttconfigurationV1],

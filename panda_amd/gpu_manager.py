@@ -587,3 +587,64 @@ def panda_ntt_gpu_lde(gm: PandaGpuManager, polys, omega_N, log_n: int, log_blowu
             if d:
                 lib.panda_free(d)
     return out
+
+
+def _stage_polys(gm: PandaGpuManager, polys):
+    """equal-length coefficient arrays -> (device buffer, batch, n); the caller frees the buffer"""
+    bufs = [_as_bytes(p) for p in polys]
+    size = bufs[0].size
+    if size == 0 or size % FIELD_ELEMENT_LEN or any(b.size != size for b in bufs):
+        raise PandaGpuError("SchedulingErr")
+    lib = ffi.load()
+    d = C.c_void_p()
+    ffi.check(lib.panda_malloc(C.byref(d), len(bufs) * size), "AsyncPoolMallocErr")
+    try:
+        for k, b in enumerate(bufs):
+            ffi.check(lib.panda_memcpy_async(C.c_void_p(d.value + k * size), _ptr(b), size, gm.h2d_stream.raw), "AsyncMemcopyErr")
+        gm.wait_h2d()
+    except Exception:
+        lib.panda_free(d)
+        raise
+    return d, len(bufs), size // FIELD_ELEMENT_LEN
+
+
+def panda_poly_gpu_evaluate(gm: PandaGpuManager, polys, points, field: int = 0) -> np.ndarray:
+    """Additive: the values of equal-length coefficient arrays (any length from 1 up; field 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr)
+    at up to ffi.POLY_MAX_POINTS points in ONE library call (panda_poly_evaluate).  `points` is a (n_points, 8) uint32 array of
+    Montgomery-form elements.  The host arrays are staged into one device buffer and are not changed.  Returns a (batch, n_points, 8)
+    uint32 array, value (p, k) = polys[p] at points[k]; an empty list returns an empty (0, n_points, 8) array without a call."""
+    pts = np.ascontiguousarray(points, np.uint32).reshape(-1, 8)
+    if len(polys) == 0:
+        return np.empty((0, len(pts), 8), np.uint32)
+    lib = ffi.load()
+    d, batch, n = _stage_polys(gm, polys)
+    try:
+        values = np.empty((batch, len(pts), 8), np.uint32)
+        ffi.check(lib.panda_poly_evaluate(field, d, n, batch, _ptr(pts), len(pts), _ptr(values), gm.exec_stream.raw), "SchedulingErr")
+    finally:
+        lib.panda_free(d)
+    return values
+
+
+def panda_poly_gpu_divide(gm: PandaGpuManager, polys, point, field: int = 0):
+    """Additive: the quotients (f - f(z)) / (X - z) of equal-length coefficient arrays by ONE library call (panda_poly_divide_linear),
+    in place on the staged device copy; the host arrays are not changed.  Returns (quotients, remainders): a list of (n, 8) uint32 arrays
+    (the last element of each is zero) and a (batch, 8) uint32 array of the values f(z); an empty list returns ([], an empty (0, 8)
+    array) without a call."""
+    if len(polys) == 0:
+        return [], np.empty((0, 8), np.uint32)
+    lib = ffi.load()
+    z = np.ascontiguousarray(point, np.uint32).reshape(8)
+    d, batch, n = _stage_polys(gm, polys)
+    quotients = []
+    try:
+        remainders = np.empty((batch, 8), np.uint32)
+        ffi.check(lib.panda_poly_divide_linear(field, d, d, n, batch, _ptr(z), _ptr(remainders), gm.exec_stream.raw), "SchedulingErr")
+        size = n * FIELD_ELEMENT_LEN
+        for k in range(batch):
+            q = np.empty(size, np.uint8)
+            ffi.check(lib.panda_memcpy(_ptr(q), C.c_void_p(d.value + k * size), size), "CreateContextError")
+            quotients.append(q.view(np.uint32).reshape(-1, 8))
+    finally:
+        lib.panda_free(d)
+    return quotients, remainders
