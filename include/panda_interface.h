@@ -13,7 +13,8 @@
  * Part 2 are the four symbols the Rust side declares but the reference never defines
  * (binding.rs:14,16,54-56).  Part 3 is additive (no reference counterpart): BLS12-377 / BLS12-381 / BN254 G2 / BLS12-381 G2 / BLS12-377 G2,
  * cached-base registration and tables, the in-call upload pipeline, inverse / coset / bit-reversed NTTs, batches, the low-degree
- * extension, polynomial evaluation and division by X - z, multi-GPU halves and synthetic-input / diagnostics entry points.
+ * extension, polynomial evaluation and division by X - z, batch inversion and grand products over the scalar fields, multi-GPU halves and
+ * synthetic-input / diagnostics entry points.
  *
  * Conventions (unchanged from the reference):
  *   - return value: the HIP runtime's error code cast to unsigned; 0 = success
@@ -393,6 +394,38 @@ panda_error panda_poly_divide_linear(unsigned field, const void *d_coeffs, void 
  * point), *launches_divide = those of a division.  None depends on `batch`.  Any pointer may be NULL.  Invalid for the shapes the execute
  * calls refuse (n == 0, batch == 0, batch x n > 2^28). */
 panda_error panda_poly_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *carry_chunk, unsigned *launches_evaluate, unsigned *launches_divide);
+/* Batch inversion and grand products over the scalar fields -- the step between "columns on the device" and "quotient on the coset": the
+ * permutation (and lookup) argument's Z(w^0) = 1, Z(w^(i+1)) = Z(w^i) num_i / den_i, and the inverse of a whole vector (logUp denominators,
+ * Lagrange and barycentric weights, the 1 / (X - zeta) columns of a batched opening).  field: 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr;
+ * elements are the 32-byte Montgomery wire form of every other call.  Inputs are canonical residues, as every producer in this library
+ * writes them; a non-canonical input is outside the contract.  Each vector costs ONE field inversion: with the identities
+ *   1 / x_i = (prod_{j<i} x_j) (prod_{j>i} x_j) / prod_all x        Z_i = (prod_{j<i} num_j) (prod_{j>=i} den_j) / prod_all den
+ * both calls are three kernel launches (tile totals; one workgroup per vector over the totals, which inverts; apply) and no kernel waits
+ * for another workgroup.  The scratch (64 bytes per tile, 32 per vector) is the calling host thread's arena: a repeated call of the same
+ * shape allocates nothing, panda_ntt_tear_down releases it.  It grows with batch x ceil(n / tile), not with batch x n: a batch of very
+ * short vectors pays a tile's scratch, a workgroup of the second launch and one inversion per vector (n = 1, batch = 2^28 is legal and
+ * asks for 16 GiB); the call is built for long vectors.
+ *   panda_error_invalid_value, nothing launched, no output written: field > 2, n == 0, batch == 0, n or batch x n > 2^28, NULL d_in / d_out /
+ *     d_num, a partial overlap (all checked before any runtime call), and buffers of this library's allocators shorter than stated. */
+/* out[i] = in[i]^-1, and 0 where in[i] == 0.  n >= 1, n <= 2^28.  d_out == d_in exactly is legal (in place); any other overlap is refused.
+ * Outputs canonical.  Synchronous on return.  Bytes behind the n elements are never written. */
+panda_error panda_field_batch_inverse(unsigned field, const void *d_in, void *d_out, uint64_t n, panda_stream stream);
+/* `batch` vectors of n elements, vector p at byte p * n * 32 of d_num, d_den and d_out:
+ *   out[p][0] = 1,  out[p][i] = prod_{j < i} num[p][j] / den[p][j]  (i < n; n elements, the exclusive running product -- Z on the domain)
+ *   totals[p] (HOST, batch x 32 B, may be NULL) = prod_{j < n} num[p][j] / den[p][j]  -- one for a valid permutation
+ * d_den == NULL: the plain running product of num (no inversion of caller data; it costs what the full call costs).
+ * A vector with a zero denominator anywhere: ALL n elements of out[p] and totals[p] are zero (out[p][0] == 0 is the signal); the other
+ *   vectors of the batch are unaffected.  A zero numerator is ordinary arithmetic (zeros from the next index on, total zero).
+ * d_out may equal d_num or d_den exactly (in place); d_num == d_den is legal; every other overlap among the three ranges is refused.
+ * n >= 1 (any count, not only powers of two), batch >= 1, batch x n <= 2^28.  Outputs canonical.  Synchronous on return.  Bytes behind the
+ * `batch` vectors are never written. */
+panda_error panda_poly_grand_product(unsigned field, const void *d_num, const void *d_den, void *d_out, uint64_t n, unsigned batch,
+                                     void *totals /* HOST, batch x 32 B, may be NULL */, panda_stream stream);
+/* How the two calls run (pure host arithmetic, no device call): *tile_inverse / *tile_product = the elements one workgroup covers in the
+ * inverse / the product kernels, *carry_chunk = the tile totals the second level takes per step, *launches = the kernel launches of either
+ * call (the same for both).  None depends on `batch`.  Any pointer may be NULL.  Invalid for the shapes the execute calls refuse (n == 0,
+ * batch == 0, n or batch x n > 2^28). */
+panda_error panda_poly_product_plan(uint64_t n, unsigned batch, unsigned *tile_inverse, unsigned *tile_product, unsigned *carry_chunk, unsigned *launches);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

@@ -24,19 +24,16 @@
 
 #include "fe29.h"
 #include "panda_internal.h"
+#include "poly_elem.h"
 
 using namespace panda29;
+using namespace panda_poly; // load_elem, store_elem, lds_put, lds_get, shape_invalid, ranges_overlap
 
 namespace {
 
-typedef uint64_t u64;
-
-constexpr int NL = 9;                   // limbs of every supported scalar field
-constexpr int THREADS = 256, WAVES = 4; // per workgroup
 constexpr int E = 8;                    // coefficients per thread
 constexpr int CE = 4;                   // tile totals per thread of the carry kernel
 constexpr unsigned TILE = THREADS * E, CHUNK = THREADS * CE;
-constexpr unsigned MAX_LOG_ELEMS = 28;  // batch x n <= 2^28, as for the batched transforms
 constexpr int LADDER = 7;               // m^(RUN 2^s), s = 0 .. 6: six cross-lane steps and the wave's width
 
 // the multipliers of one launch: the step m of the recurrence and m^(RUN 2^s), RUN the elements a thread covers
@@ -45,27 +42,6 @@ struct Ladder {
     FeTw<Fr> m;
     FeTw<Fr> pw[LADDER];
 };
-
-template <class Fr>
-__device__ __forceinline__ void load_elem(Fe<Fr> &v, const u32 *__restrict__ src)
-{
-    const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-    const uint4 lo = s4[0], hi = s4[1];
-    const u32 w8[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    fe_unpack(v, w8);
-}
-
-// any value the kernels hold (limbs < 2^32, < 2^9 p) -> canonical -> 32 bytes
-template <class Fr>
-__device__ __forceinline__ void store_elem(u32 *__restrict__ dst, Fe<Fr> v)
-{
-    fe_reduce_small(v);
-    u32 w8[8];
-    fe_pack(w8, v);
-    uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-    d4[0] = make_uint4(w8[0], w8[1], w8[2], w8[3]);
-    d4[1] = make_uint4(w8[4], w8[5], w8[6], w8[7]);
-}
 
 // v += w t, normalised
 template <class Fr>
@@ -118,18 +94,6 @@ template <class Fr>
 __device__ __forceinline__ void wave_suffix_scan(Fe<Fr> &v, const Ladder<Fr> &L, unsigned lane)
 {
     wave_reduce(v, L, lane); // the same steps; lanes_up's zeros make every lane's partial sum exact
-}
-
-__device__ __forceinline__ void lds_put(u32 *s, const u32 *l)
-{
-#pragma unroll
-    for (int i = 0; i < NL; i++) s[i] = l[i];
-}
-template <class Fr>
-__device__ __forceinline__ void lds_get(Fe<Fr> &r, const u32 *s)
-{
-#pragma unroll
-    for (int i = 0; i < NL; i++) r.l[i] = s[i];
 }
 
 // The workgroup's 256 runs x[t][0 .. RUN) stand for THREADS * RUN consecutive elements of the recurrence s_i = x_i + m s_(i+1); `edge`
@@ -289,18 +253,6 @@ void make_ladder(Ladder<Fr> &L, const Fe<Fr> &m, unsigned run, Fe<Fr> *next)
     fe_sqr(pw, pw); // run * 2^8
     static_assert(THREADS == 256, "the ladder's last rung squared twice is the workgroup's width");
     if (next) *next = pw;
-}
-
-bool shape_invalid(u64 n, unsigned batch)
-{
-    const u64 cap = (u64)1 << MAX_LOG_ELEMS;
-    return n == 0 || batch == 0 || n > cap || (u64)batch * n > cap;
-}
-
-bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 // the 256-bit value of a wire element is below the modulus

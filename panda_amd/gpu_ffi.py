@@ -106,6 +106,7 @@ ADDITIVE_SYMBOLS = [
     "panda_ntt_execute_batch", "panda_ntt_batch_plan",
     "panda_ntt_execute_lde", "panda_ntt_lde_plan",
     "panda_poly_evaluate", "panda_poly_divide_linear", "panda_poly_plan",
+    "panda_field_batch_inverse", "panda_poly_grand_product", "panda_poly_product_plan",
 ]
 ALL_SYMBOLS = REFERENCE_SYMBOLS + RUST_ONLY_SYMBOLS + ADDITIVE_SYMBOLS
 
@@ -150,6 +151,8 @@ def load() -> C.CDLL:
         "panda_ntt_execute_lde": [u, NttconfigurationV1, vp, u, u, vp, u], "panda_ntt_lde_plan": [u, u, u, u, C.POINTER(u), C.POINTER(u)],
         "panda_poly_evaluate": [u, vp, C.c_uint64, u, vp, u, vp, PandaStream], "panda_poly_divide_linear": [u, vp, vp, C.c_uint64, u, vp, vp, PandaStream],
         "panda_poly_plan": [C.c_uint64, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)],
+        "panda_field_batch_inverse": [u, vp, vp, C.c_uint64, PandaStream], "panda_poly_grand_product": [u, vp, vp, vp, C.c_uint64, u, vp, PandaStream],
+        "panda_poly_product_plan": [C.c_uint64, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)],
         "panda_msm_register_bases": [u, vp, u, PandaStream], "panda_msm_unregister_bases": [vp], "panda_msm_precompute_bases": [u, vp, u, u, PandaStream],
         "panda_msm_registered_info": [vp, C.POINTER(u), C.POINTER(u), C.POINTER(sz)], "panda_msm_set_chunk_entries": [u], "panda_msm_set_overlap": [u, u], "panda_msm_set_accumulate_variant": [u], "panda_msm_set_wide_merge": [u], "panda_msm_set_reduce_group": [u], "panda_msm_plain_window_plan": [u, u, C.POINTER(u), C.POINTER(u)], "panda_msm_verify_registered": [vp, PandaStream], "panda_msm_set_paranoid": [u], "panda_msm_set_phase_timing": [u], "panda_msm_setup_bls12_377": [], "panda_msm_execute_bls12_377": [MSMConfiguration], "panda_msm_execute_bls12_377_host": [MSMConfiguration],
         "panda_msm_set_window_bits": [u], "panda_msm_last_phase_ms": [C.POINTER(C.c_float)], "panda_ntt_last_device_ms": [C.POINTER(C.c_float)], "panda_ntt_pass_plan": [u, C.POINTER(C.c_uint), C.POINTER(C.c_uint)], "panda_ntt_set_streamed_tables": [u], "panda_ntt_execute_bn254_inverse": [NttconfigurationV1], "panda_ntt_execute_bls12_377_v1": [NttconfigurationV1], "panda_ntt_execute_bls12_377_inverse": [NttconfigurationV1],

@@ -648,3 +648,55 @@ def panda_poly_gpu_divide(gm: PandaGpuManager, polys, point, field: int = 0):
     finally:
         lib.panda_free(d)
     return quotients, remainders
+
+
+def _download_vectors(lib, d, batch, n):
+    """the `batch` vectors of n elements at d -> a list of (n, 8) uint32 arrays"""
+    size = n * FIELD_ELEMENT_LEN
+    out = []
+    for k in range(batch):
+        v = np.empty(size, np.uint8)
+        ffi.check(lib.panda_memcpy(_ptr(v), C.c_void_p(d.value + k * size), size), "CreateContextError")
+        out.append(v.view(np.uint32).reshape(-1, 8))
+    return out
+
+
+def panda_field_gpu_batch_inverse(gm: PandaGpuManager, values, field: int = 0):
+    """Additive: the inverses of equal-length arrays of Montgomery-form elements (any length from 1 up; field 0 BN254 Fr, 1 BLS12-377 Fr,
+    2 BLS12-381 Fr), zero for zero, by ONE library call (panda_field_batch_inverse over the staged arrays end to end, in place on the
+    device copy); the host arrays are not changed.  Returns a list of (n, 8) uint32 arrays; an empty list returns [] without a call."""
+    if len(values) == 0:
+        return []
+    lib = ffi.load()
+    d, batch, n = _stage_polys(gm, values)
+    try:
+        ffi.check(lib.panda_field_batch_inverse(field, d, d, batch * n, gm.exec_stream.raw), "SchedulingErr")
+        return _download_vectors(lib, d, batch, n)
+    finally:
+        lib.panda_free(d)
+
+
+def panda_poly_gpu_grand_product(gm: PandaGpuManager, nums, dens, field: int = 0):
+    """Additive: the exclusive running products Z_0 = 1, Z_i = prod_{j < i} nums[p][j] / dens[p][j] of equal-length arrays by ONE library
+    call (panda_poly_grand_product, in place on the staged numerators); dens=None is the plain running product of nums.  The host arrays
+    are not changed.  Returns (products, totals): a list of (n, 8) uint32 arrays and a (batch, 8) uint32 array of the full products; a
+    vector with a zero denominator comes back all zero.  An empty list returns ([], an empty (0, 8) array) without a call."""
+    if len(nums) == 0:
+        return [], np.empty((0, 8), np.uint32)
+    if dens is not None and len(dens) != len(nums):
+        raise PandaGpuError("SchedulingErr")
+    lib = ffi.load()
+    d_num, batch, n = _stage_polys(gm, nums)
+    d_den = None
+    try:
+        if dens is not None:
+            d_den, batch_den, n_den = _stage_polys(gm, dens)
+            if (batch_den, n_den) != (batch, n):
+                raise PandaGpuError("SchedulingErr")
+        totals = np.empty((batch, 8), np.uint32)
+        ffi.check(lib.panda_poly_grand_product(field, d_num, d_den, d_num, n, batch, _ptr(totals), gm.exec_stream.raw), "SchedulingErr")
+        return _download_vectors(lib, d_num, batch, n), totals
+    finally:
+        lib.panda_free(d_num)
+        if d_den is not None:
+            lib.panda_free(d_den)
