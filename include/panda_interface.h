@@ -426,6 +426,55 @@ panda_error panda_poly_grand_product(unsigned field, const void *d_num, const vo
  * call (the same for both).  None depends on `batch`.  Any pointer may be NULL.  Invalid for the shapes the execute calls refuse (n == 0,
  * batch == 0, n or batch x n > 2^28). */
 panda_error panda_poly_product_plan(uint64_t n, unsigned batch, unsigned *tile_inverse, unsigned *tile_product, unsigned *carry_chunk, unsigned *launches);
+/* Fused sum-of-products evaluation over device columns -- the "quotient on the coset" itself and every other element-wise polynomial
+ * expression of a prover's round: the gate q_L a + q_R b + q_M a b + q_O c + q_C, the permutation check Z(wX) prod(..) - Z(X) prod(..),
+ * Groth16's a b - c, each times the inverse of the vanishing polynomial; the fold sum_k v^k f_k in front of a batched opening; the
+ * linearisation polynomial; the (a + beta id + gamma) factor columns panda_poly_grand_product takes.  For vector p < batch, index i < n:
+ *   out[p][i] = s(p, i) * sum_{t < n_terms} coeff_t * prod_{f < degree_t} column[c_tf][p][(i + r_tf) mod n]
+ * in ONE kernel launch and one pass over the columns; nothing intermediate goes to device memory.
+ *   field: 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr.  Elements are the 32-byte Montgomery wire form of every other call; inputs are
+ *     canonical residues, outputs are canonical.  n is ANY count from 1 up, batch >= 1, n and batch x n <= 2^28.
+ *   columns: HOST array of n_columns DEVICE pointers, each to batch x n x 32 bytes, vector p at byte p x n x 32, read only.  Columns may
+ *     be equal to each other or overlap each other freely (pointers into one extended buffer at different polynomials).
+ *   coeffs (HOST, n_terms x 32 B), scales (HOST, n_scales x 32 B): wire elements below the modulus.  degrees (HOST, n_terms): the factor
+ *     count of each term, 0 = a constant term.  factors (HOST, sum of the degrees, term after term): the column index and the rotation
+ *     of each factor.  A rotation is any int32_t, reduced mod n on the host; it wraps inside vector p and never reaches vector p +- 1.
+ *   scale_mode: PANDA_SOP_SCALE_NONE s = 1 (scales may be NULL); PANDA_SOP_SCALE_PER_VECTOR s = scales[p mod n_scales];
+ *     PANDA_SOP_SCALE_CYCLIC s = scales[i mod n_scales].  With PANDA_NTT_LDE_COSET_MAJOR one extended polynomial is batch = B vectors
+ *     of n, X -> wX is rotation +1 and 1 / Z_H is the constant 1 / (g^n w_N^(i n) - 1) on coset i: PER_VECTOR with n_scales = B.  With
+ *     PANDA_NTT_LDE_NATURAL it is one vector of N, rotation +B, CYCLIC with n_scales = B.
+ *   d_out (DEVICE, batch x n x 32 B) may equal a column's pointer exactly (in place) if and only if every factor on every column that
+ *     overlaps d_out has a rotation that is 0 mod n; any partial overlap of d_out with a column is refused.
+ *   Synchronous on return.  Bytes behind the `batch` vectors are never written.  The program (about 5 KB: pointers, reduced rotations,
+ *     term offsets, coefficients and scales with the wire form's constants folded in) goes to the calling host thread's arena scratch: a
+ *     repeated call allocates nothing, panda_ntt_tear_down releases it.
+ *   panda_error_invalid_value, nothing launched, nothing written: field > 2, n == 0, batch == 0, n or batch x n > 2^28, NULL expr / d_out /
+ *     columns / coeffs / degrees or a NULL column pointer, factors NULL while the degrees sum to more than 0, n_columns 0 or >
+ *     PANDA_SOP_MAX_COLUMNS, n_terms 0 or > PANDA_SOP_MAX_TERMS, the degrees summing to more than PANDA_SOP_MAX_FACTORS, a factor's column
+ *     index >= n_columns, scale_mode > 2, a scale mode other than NONE with scales NULL or n_scales 0 or > PANDA_SOP_MAX_SCALES, a
+ *     coefficient or scale >= the modulus, the overlaps above (all checked before any runtime call), and buffers of this library's
+ *     allocators shorter than stated. */
+#define PANDA_SOP_MAX_COLUMNS 32
+#define PANDA_SOP_MAX_TERMS   64
+#define PANDA_SOP_MAX_FACTORS 256   /* sum of the terms' degrees */
+#define PANDA_SOP_MAX_SCALES  16    /* 2^PANDA_NTT_LDE_MAX_LOG_BLOWUP */
+#define PANDA_SOP_SCALE_NONE 0u
+#define PANDA_SOP_SCALE_PER_VECTOR 1u   /* s = scales[p mod n_scales] */
+#define PANDA_SOP_SCALE_CYCLIC 2u       /* s = scales[i mod n_scales] */
+typedef struct panda_sop_factor { uint32_t column; int32_t rotation; } panda_sop_factor;
+typedef struct panda_sop_expression {
+    const void *const *columns;      /* HOST array of n_columns DEVICE pointers, each batch x n x 32 B, read only */
+    const void *coeffs;              /* HOST, n_terms x 32 B, Montgomery wire form, value < modulus */
+    const unsigned *degrees;         /* HOST, n_terms; 0 = a constant term */
+    const panda_sop_factor *factors; /* HOST, sum(degrees) entries, term after term */
+    const void *scales;              /* HOST, n_scales x 32 B, or NULL with SCALE_NONE */
+    unsigned n_columns, n_terms, n_scales, scale_mode;
+} panda_sop_expression;
+panda_error panda_poly_sum_of_products(unsigned field, const panda_sop_expression *expr, void *d_out, uint64_t n, unsigned batch, panda_stream stream);
+/* How the call runs (pure host arithmetic, no device call): *tile = the elements one workgroup covers, *launches = its kernel launches
+ * (1).  Neither depends on `batch`.  Either pointer may be NULL.  Invalid for the shapes the call refuses (n == 0, batch == 0, n or
+ * batch x n > 2^28). */
+panda_error panda_poly_sum_of_products_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *launches);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

@@ -27,7 +27,7 @@
 #include "poly_elem.h"
 
 using namespace panda29;
-using namespace panda_poly; // load_elem, store_elem, lds_put, lds_get, shape_invalid, ranges_overlap
+using namespace panda_poly; // load_elem, store_elem, lds_put, lds_get, shape_invalid, ranges_overlap, wire_below_modulus
 
 namespace {
 
@@ -253,15 +253,6 @@ void make_ladder(Ladder<Fr> &L, const Fe<Fr> &m, unsigned run, Fe<Fr> *next)
     fe_sqr(pw, pw); // run * 2^8
     static_assert(THREADS == 256, "the ladder's last rung squared twice is the workgroup's width");
     if (next) *next = pw;
-}
-
-// the 256-bit value of a wire element is below the modulus
-template <class Fr>
-bool wire_below_modulus(const u32 *w)
-{
-    for (int i = Fr::L - 1; i >= 0; i--)
-        if (w[i] != Fr::PW[i]) return w[i] < Fr::PW[i];
-    return false;
 }
 
 bool point_valid(unsigned field, const void *pt)

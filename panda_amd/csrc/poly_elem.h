@@ -1,5 +1,5 @@
-// poly_elem.h -- what poly.hip and poly_product.hip share: the 32-byte element load / store, the LDS moves of a 9-limb value and the
-// shape and overlap checks of their entry points.
+// poly_elem.h -- what poly.hip, poly_product.hip and poly_terms.hip share: the 32-byte element load / store, the LDS moves of a 9-limb
+// value and the shape, overlap and modulus checks of their entry points.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -53,6 +53,15 @@ inline bool shape_invalid(u64 n, unsigned batch)
 {
     const u64 cap = (u64)1 << MAX_LOG_ELEMS;
     return n == 0 || batch == 0 || n > cap || (u64)batch * n > cap;
+}
+
+// the 256-bit value of a wire element is below the modulus
+template <class Fr>
+inline bool wire_below_modulus(const u32 *w)
+{
+    for (int i = Fr::L - 1; i >= 0; i--)
+        if (w[i] != Fr::PW[i]) return w[i] < Fr::PW[i];
+    return false;
 }
 
 inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)

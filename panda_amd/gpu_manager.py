@@ -700,3 +700,40 @@ def panda_poly_gpu_grand_product(gm: PandaGpuManager, nums, dens, field: int = 0
         lib.panda_free(d_num)
         if d_den is not None:
             lib.panda_free(d_den)
+
+
+def panda_poly_gpu_sum_of_products(gm: PandaGpuManager, columns, terms, field: int = 0, scales=None, scale_mode: int = 0) -> np.ndarray:
+    """Additive: out[p][i] = s(p, i) * sum_t coeff_t * prod_f columns[c_tf][p][(i + r_tf) mod n] by ONE library call
+    (panda_poly_sum_of_products): gates, permutation checks, a b - c, folds with powers of a challenge -- any sum of monomials over
+    columns of Montgomery-form elements (field 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr).  `columns` is a list of equally shaped uint32
+    arrays, (n, 8) or (batch, n, 8); `terms` a list of (coeff, [(column, rotation), ...]) with coeff an 8-word element and an empty
+    factor list for a constant term; `scales` an (n_scales, 8) array with scale_mode ffi.SOP_SCALE_PER_VECTOR (s = scales[p mod n_scales])
+    or ffi.SOP_SCALE_CYCLIC (s = scales[i mod n_scales]).  The host arrays are staged into one device buffer and are not changed.
+    Returns an array of the columns' shape."""
+    cols = [np.ascontiguousarray(c, np.uint32) for c in columns]
+    if not cols or not terms or cols[0].ndim not in (2, 3) or cols[0].shape[-1] != 8 or any(c.shape != cols[0].shape for c in cols):
+        raise PandaGpuError("SchedulingErr")
+    shape = cols[0].shape
+    batch, n = (1, shape[0]) if len(shape) == 2 else shape[:2]
+    coeffs = np.ascontiguousarray([np.asarray(k, np.uint32).reshape(8) for k, _ in terms], np.uint32)
+    degrees = (C.c_uint * len(terms))(*[len(fs) for _, fs in terms])
+    flat = [(c, r) for _, fs in terms for c, r in fs]
+    factors = (ffi.SopFactor * max(len(flat), 1))(*[ffi.SopFactor(c, r) for c, r in flat])
+    sc = None if scales is None else np.ascontiguousarray(scales, np.uint32).reshape(-1, 8)
+    lib = ffi.load()
+    d, _, _ = _stage_polys(gm, cols)
+    d_out = C.c_void_p()
+    try:
+        size = batch * n * FIELD_ELEMENT_LEN
+        ffi.check(lib.panda_malloc(C.byref(d_out), size), "AsyncPoolMallocErr")
+        ptrs = (C.c_void_p * len(cols))(*[d.value + k * size for k in range(len(cols))])
+        expr = ffi.SopExpression(ptrs, _ptr(coeffs), degrees, factors, None if sc is None else _ptr(sc), len(cols), len(terms),
+                                 0 if sc is None else len(sc), scale_mode)
+        ffi.check(lib.panda_poly_sum_of_products(field, C.byref(expr), d_out, n, batch, gm.exec_stream.raw), "SchedulingErr")
+        out = np.empty(shape, np.uint32)
+        ffi.check(lib.panda_memcpy(_ptr(out), d_out, size), "CreateContextError")
+        return out
+    finally:
+        lib.panda_free(d)
+        if d_out:
+            lib.panda_free(d_out)
