@@ -13,7 +13,8 @@
  * Part 2 are the four symbols the Rust side declares but the reference never defines
  * (binding.rs:14,16,54-56).  Part 3 is additive (no reference counterpart): BLS12-377 / BLS12-381 / BN254 G2 / BLS12-381 G2 / BLS12-377 G2,
  * cached-base registration and tables, the in-call upload pipeline, inverse / coset / bit-reversed NTTs, batches, the low-degree
- * extension, polynomial evaluation and division by X - z, batch inversion and grand products over the scalar fields, multi-GPU halves and
+ * extension, polynomial evaluation and division by X - z, batch inversion and grand products over the scalar fields, fused sums of
+ * products, logUp lookup support (multiplicities and running sums), multi-GPU halves and
  * synthetic-input / diagnostics entry points.
  *
  * Conventions (unchanged from the reference):
@@ -475,6 +476,62 @@ panda_error panda_poly_sum_of_products(unsigned field, const panda_sop_expressio
  * (1).  Neither depends on `batch`.  Either pointer may be NULL.  Invalid for the shapes the call refuses (n == 0, batch == 0, n or
  * batch x n > 2^28). */
 panda_error panda_poly_sum_of_products_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *launches);
+/* logUp lookup support -- the two steps of a logarithmic-derivative lookup argument that are not arithmetic on columns.  The whole chain
+ * stays on the device: panda_lookup_multiplicities (m) -> panda_poly_sum_of_products (alpha + f, alpha + t) -> panda_field_batch_inverse ->
+ * panda_poly_sum_of_products (h_i = sum_k 1 / (alpha + f_k,i) - m_i / (alpha + t_i)) -> panda_poly_running_sum (Z, and the total that must
+ * be zero).  field: 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr; elements are the 32-byte canonical Montgomery wire form of every other
+ * call, a non-canonical input is outside the contract.
+ *
+ * Multiplicities.  Equality is equality of the 256-bit wire value; zero is an ordinary value.  With j0 the FIRST index at which a table
+ * value occurs, d_mult[j0] is the wire form of the number of pairs (column c, index i) with columns[c][i] == table[j0], and d_mult[j] is
+ * the wire zero for every later duplicate j of that value: sum_j m_j / (alpha + t_j) = sum 1 / (alpha + f) whatever the table repeats.
+ *   *missing (HOST, may be NULL) = the number of pairs (c, i) whose value occurs nowhere in the table; *first_missing (HOST, may be NULL) =
+ *     (c << 32) | i of the lexicographically smallest such pair, UINT64_MAX when there is none.  A missing value is data, not an error:
+ *     the call still returns panda_success.
+ *   Every output is deterministic: d_mult is byte for byte the same on every run.
+ *   n_table >= 1, n >= 1, n_columns in 1..PANDA_LOOKUP_MAX_COLUMNS, n_table <= 2^28 and n_columns x n <= 2^28 (a count fits a u32 and one
+ *     29-bit limb).  columns: HOST array of n_columns DEVICE pointers, n elements each.  Columns may be equal to each other, overlap each
+ *     other and overlap the table; the table and the columns are read only; d_mult may overlap none of them.  Synchronous on return.
+ *     Bytes behind d_mult's n_table elements are never written.
+ *   The join is an open-addressing hash table of 2^log_slots >= 2 n_table slots (12 bytes each, and 4 bytes per table row) in the
+ *     calling host thread's arena scratch: a repeated call of the same shape allocates nothing, panda_ntt_tear_down releases it.  Three
+ *     kernel launches (build, probe, finish) on the caller's stream; no kernel waits for another workgroup.
+ *   panda_error_invalid_value, nothing launched, no host output written: field > 2, n_table == 0 or > 2^28, n == 0, n or n_columns x n >
+ *     2^28, n_columns 0 or > PANDA_LOOKUP_MAX_COLUMNS, NULL d_table / columns / d_mult or a NULL column pointer, d_mult overlapping the
+ *     table or a column as address ranges (all checked before any runtime call), and buffers of this library's allocators shorter than
+ *     stated. */
+#define PANDA_LOOKUP_MAX_COLUMNS 32
+panda_error panda_lookup_multiplicities(unsigned field, const void *d_table, uint64_t n_table,
+                                        const void *const *columns /* HOST array of n_columns DEVICE pointers, n elements each */,
+                                        unsigned n_columns, uint64_t n, void *d_mult /* DEVICE, n_table x 32 B */,
+                                        uint64_t *missing /* HOST, may be NULL */, uint64_t *first_missing /* HOST, may be NULL */,
+                                        panda_stream stream);
+/* How the call runs (pure host arithmetic, no device call): *log_slots = log2 of the hash table's slot count (2^log_slots >= 2 n_table),
+ * *scratch_bytes = the arena bytes the call reserves, *launches = its kernel launches, not counting memsets (3).  Any pointer may be
+ * NULL.  Invalid for exactly the shapes the execute call refuses. */
+panda_error panda_lookup_plan(uint64_t n_table, unsigned n_columns, uint64_t n, unsigned *log_slots, size_t *scratch_bytes, unsigned *launches);
+/* The slot the library's hash gives a wire element (HOST, 32 B) in a table of 2^log_slots slots: where its walk starts (pure host
+ * arithmetic; the kernels run the same code).  For tests that build collision chains and wrap-around cases on purpose.  Invalid for
+ * field > 2, a NULL pointer, log_slots 0 or > 29. */
+panda_error panda_lookup_home_slot(unsigned field, const void *elem /* HOST, 32 B */, unsigned log_slots, uint64_t *slot);
+/* `batch` vectors of n elements, vector p at byte p * n * 32 of d_in and d_out:
+ *   out[p][0] = 0,  out[p][i] = sum_{j < i} in[p][j]  (i < n; n elements, the exclusive running sum -- logUp's Z on the domain)
+ *   totals[p] (HOST, batch x 32 B, may be NULL) = sum_{j < n} in[p][j]  -- zero for a valid logUp argument; asked for alone it is the
+ *     plain sum of a vector (barycentric evaluation, every "does it sum to zero" check)
+ * d_out == NULL computes the totals only and writes no device memory of the caller's; d_out and totals both NULL is refused.  d_out ==
+ * d_in exactly is legal (in place); any other overlap is refused.  Any n >= 1, batch >= 1, batch x n <= 2^28.  Inputs canonical, outputs
+ * canonical.  Synchronous on return.  Bytes behind the `batch` vectors are never written.  Three kernel launches (tile sums; one workgroup
+ * per vector over the sums; apply), two for the totals alone; no kernel waits for another workgroup.  The scratch (32 bytes per tile and
+ * per vector) is the calling host thread's arena.
+ *   panda_error_invalid_value, nothing launched, no output written: field > 2, n == 0, batch == 0, n or batch x n > 2^28, NULL d_in, d_out
+ *     and totals both NULL, a partial overlap (all checked before any runtime call), and buffers of this library's allocators shorter
+ *     than stated. */
+panda_error panda_poly_running_sum(unsigned field, const void *d_in, void *d_out /* may be NULL: totals only */, uint64_t n, unsigned batch,
+                                   void *totals /* HOST, batch x 32 B, may be NULL */, panda_stream stream);
+/* How the call runs (pure host arithmetic, no device call): *tile = the elements one workgroup covers, *carry_chunk = the tile sums the
+ * second level takes per step, *launches_scan / *launches_total = the kernel launches with and without d_out (3, 2).  None depends on
+ * `batch`.  Any pointer may be NULL.  Invalid for the shapes the execute call refuses (n == 0, batch == 0, n or batch x n > 2^28). */
+panda_error panda_poly_running_sum_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *carry_chunk, unsigned *launches_scan, unsigned *launches_total);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

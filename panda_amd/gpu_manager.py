@@ -702,6 +702,48 @@ def panda_poly_gpu_grand_product(gm: PandaGpuManager, nums, dens, field: int = 0
             lib.panda_free(d_den)
 
 
+def panda_lookup_gpu_multiplicities(gm: PandaGpuManager, table, columns, field: int = 0):
+    """Additive: the logUp multiplicities of a lookup by ONE library call (panda_lookup_multiplicities): `table` is an (n_table, 8) uint32
+    array of Montgomery-form elements, `columns` a list of 1..ffi.LOOKUP_MAX_COLUMNS equal-length (n, 8) arrays.  Returns (mult, missing,
+    first_missing): mult (n_table, 8) holds at the first row of every table value the wire form of the number of column elements equal
+    to it and zero at its later duplicates; missing counts the column elements found nowhere in the table and first_missing is
+    (column << 32) | index of the smallest such pair, 2^64 - 1 when there is none.  The host arrays are not changed."""
+    if len(columns) == 0 or len(columns) > ffi.LOOKUP_MAX_COLUMNS:
+        raise PandaGpuError("SchedulingErr")
+    lib = ffi.load()
+    d_table, _, n_table = _stage_polys(gm, [table])
+    d_cols = d_mult = None
+    try:
+        d_cols, n_columns, n = _stage_polys(gm, columns)
+        d_mult = C.c_void_p()
+        ffi.check(lib.panda_malloc(C.byref(d_mult), n_table * FIELD_ELEMENT_LEN), "AsyncPoolMallocErr")
+        ptrs = (C.c_void_p * n_columns)(*[d_cols.value + k * n * FIELD_ELEMENT_LEN for k in range(n_columns)])
+        missing, first = C.c_uint64(0), C.c_uint64(0)
+        ffi.check(lib.panda_lookup_multiplicities(field, d_table, n_table, ptrs, n_columns, n, d_mult, C.byref(missing), C.byref(first), gm.exec_stream.raw),
+                  "SchedulingErr")
+        return _download_vectors(lib, d_mult, 1, n_table)[0], missing.value, first.value
+    finally:
+        for d in (d_table, d_cols, d_mult):
+            if d is not None:
+                lib.panda_free(d)
+
+
+def panda_poly_gpu_running_sum(gm: PandaGpuManager, vectors, field: int = 0):
+    """Additive: the exclusive running sums Z_0 = 0, Z_i = sum_{j < i} vectors[p][j] of equal-length arrays by ONE library call
+    (panda_poly_running_sum, in place on the staged vectors).  The host arrays are not changed.  Returns (sums, totals): a list of (n, 8)
+    uint32 arrays and a (batch, 8) uint32 array of the full sums.  An empty list returns ([], an empty (0, 8) array) without a call."""
+    if len(vectors) == 0:
+        return [], np.empty((0, 8), np.uint32)
+    lib = ffi.load()
+    d, batch, n = _stage_polys(gm, vectors)
+    try:
+        totals = np.empty((batch, 8), np.uint32)
+        ffi.check(lib.panda_poly_running_sum(field, d, d, n, batch, _ptr(totals), gm.exec_stream.raw), "SchedulingErr")
+        return _download_vectors(lib, d, batch, n), totals
+    finally:
+        lib.panda_free(d)
+
+
 def panda_poly_gpu_sum_of_products(gm: PandaGpuManager, columns, terms, field: int = 0, scales=None, scale_mode: int = 0) -> np.ndarray:
     """Additive: out[p][i] = s(p, i) * sum_t coeff_t * prod_f columns[c_tf][p][(i + r_tf) mod n] by ONE library call
     (panda_poly_sum_of_products): gates, permutation checks, a b - c, folds with powers of a challenge -- any sum of monomials over
