@@ -1,17 +1,10 @@
 // lookup.h -- what the kernels of lookup.hip share with the host: the hash of panda_lookup_multiplicities' join (the kernels and
-// panda_lookup_home_slot run THIS code, so they cannot drift apart), the count -> wire conversion of its last launch and the addition
-// chain of panda_poly_running_sum; kept apart from the kernels so that a host program can run all three
-// (tests/host_check/lookup_host.cpp, under FE29_CHECK).  DESIGN.md 5.6.
+// panda_lookup_home_slot run THIS code, so they cannot drift apart) and the count -> wire conversion of its last launch; kept apart
+// from the kernels so that a host program can run both (tests/host_check/lookup_host.cpp, under FE29_CHECK).  DESIGN.md 5.6.
 //
-// Bounds of the additions (contract at the top of fe29.h; the three scalar fields have nine limbs and p < 2^255):
-//   loaded element    fe_unpack of a canonical residue                          tight, < p
-//   add_canon(a, b)   a, b canonical: limb-wise sum, limbs < 2^30, value < 2p;  fe_carry (carries <= 1) -> tight; fe_reduce_once
-//                                                                               canonical, < p
-//   sum_run<E>        E <= RUN_MAX = 7 canonical elements added limb-wise, no carries: limbs 0..7 <= 7 (2^29 - 1) < 2^32 - 8, the top
-//                     limb < 7 2^24, value < 7p < 2^9 p: what fe_reduce_small takes -> canonical, < p
+// Bounds (contract at the top of fe29.h; the three scalar fields have nine limbs and p < 2^255):
 //   count -> wire     fe_mul((c, 0, .., 0), K): c <= 2^28 < 2^29 is a tight limb vector, K canonical: c K < 2^29 p < 0.9 R p
 //                                                                               tight, < 2p; store_elem -> canonical
-// Every value that crosses a lane, LDS or memory is canonical, so the number of elements, tiles and chunks does not enter.
 #pragma once
 #include <stdint.h>
 
@@ -26,7 +19,6 @@ using panda29::u32;
 typedef uint64_t u64;
 
 constexpr unsigned MAX_LOG_SLOTS = 29; // 2^29 >= 2 x 2^28 table rows
-constexpr int RUN_MAX = 7;             // elements sum_run may add before it reduces
 
 // ------------------------------------------------------------------------------- the hash
 // Two 32-bit words out of all eight of the element: `h`, whose top log_slots bits are the home slot, and a fingerprint `fp` kept beside
@@ -98,29 +90,6 @@ PANDA_HD void count_to_wire(Fe<Fr> &r, u32 c, const Fe<Fr> &K)
     panda29::fe_zero(v);
     v.l[0] = c;
     panda29::fe_mul(r, v, K);
-}
-
-// ------------------------------------------------------------------------------- the running sum's additions
-// a, b canonical -> a + b canonical
-template <class Fr>
-PANDA_HD void add_canon(Fe<Fr> &r, const Fe<Fr> &a, const Fe<Fr> &b)
-{
-    Fe<Fr> t;
-    panda29::fe_add_nr(t, a, b);
-    panda29::fe_carry(t);
-    panda29::fe_reduce_once(t);
-    r = t;
-}
-// the sum of E <= RUN_MAX canonical elements, canonical
-template <class Fr, int E>
-PANDA_HD void sum_run(Fe<Fr> &g, const Fe<Fr> (&x)[E])
-{
-    static_assert(E >= 1 && E <= RUN_MAX, "sum_run: limbs must stay below 2^32 - 8");
-    Fe<Fr> t = x[0];
-#pragma unroll
-    for (int e = 1; e < E; e++) panda29::fe_add_nr(t, t, x[e]);
-    panda29::fe_reduce_small(t);
-    g = t;
 }
 
 } // namespace panda_lookup

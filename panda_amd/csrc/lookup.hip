@@ -1,5 +1,5 @@
-// lookup.hip -- the two steps of a logUp lookup argument that are not field arithmetic on columns (panda_lookup_multiplicities,
-// panda_lookup_plan, panda_lookup_home_slot, panda_poly_running_sum, panda_poly_running_sum_plan).
+// lookup.hip -- the join of a logUp lookup argument (panda_lookup_multiplicities, panda_lookup_plan, panda_lookup_home_slot).
+// The argument's other step that is not field arithmetic on columns, the running sum, is poly_sum.hip.
 //
 // Multiplicities: m_j = the number of (column, index) pairs whose element equals table[j], counted at the FIRST row of every table value
 // and zero at its later duplicates.  A join through an open-addressing hash table of 2^log_slots >= 2 n_table slots in the arena, linear
@@ -18,12 +18,6 @@
 //   launch 3  k_lookup_finish  one thread per table row j: the counter of the slot its walk ended in if that slot holds j, else zero;
 //                              count -> wire by one fe_mul with a host constant, store_elem.
 // Why the result does not depend on the arrival order: DESIGN.md 5.6.
-//
-// Running sum: out[p][0] = 0, out[p][i] = sum_{j < i} in[p][j], totals[p] = the whole sum.  Reduce-then-scan over tiles of
-// TILE = THREADS * E elements, the launch structure of poly_product.hip: k_sum_totals (tile sums), k_sum_seeds (one workgroup per
-// vector: exclusive prefix sums of the tile sums in place, the grand sum to the values), k_sum_apply (in-tile scan from the seed; a thread
-// stores only the indices it loaded, so d_out may be d_in).  Totals only: the first two launches, no seeds stored.  A sum of wire
-// residues is the wire residue of the sum: no constants.  Bounds: lookup.h.
 #include <string.h>
 
 #include "fe29.h"
@@ -36,8 +30,6 @@ using namespace panda_poly;
 using namespace panda_lookup;
 
 namespace {
-
-// =============================================================================== multiplicities
 
 constexpr u64 EMPTY = ~(u64)0;
 constexpr u32 NO_SLOT = ~(u32)0;
@@ -226,156 +218,6 @@ bool lookup_shape_invalid(u64 n_table, unsigned n_columns, u64 n)
     return n_table == 0 || n_table > cap || n_columns == 0 || n_columns > PANDA_LOOKUP_PROGRAM_COLUMNS || n == 0 || n > cap || (u64)n_columns * n > cap;
 }
 
-// =============================================================================== running sum
-
-constexpr int E = 4;  // elements per thread (lookup.h: RUN_MAX)
-constexpr int CE = 4; // tile sums per thread of the seed kernel
-constexpr unsigned TILE = THREADS * E, CHUNK = THREADS * CE;
-static_assert(E <= RUN_MAX && CE <= RUN_MAX, "a thread's run must stay within sum_run's bound");
-
-// inclusive sum scan of the wave: lane l <- sum_{u <= l} v_u, canonical in and out
-template <class Fr>
-__device__ __forceinline__ void wave_scan_add(Fe<Fr> &v, unsigned lane)
-{
-#pragma unroll
-    for (int s = 0; s < 6; s++) {
-        const unsigned d = 1u << s;
-        Fe<Fr> t, sum;
-#pragma unroll
-        for (int i = 0; i < NL; i++) t.l[i] = __shfl_up(v.l[i], d, 64);
-        add_canon(sum, v, t);
-        fe_select(v, lane >= d, sum, v);
-    }
-}
-
-// g is the sum of the calling thread's run.  mine <- seed plus the g of every thread before the caller, total <- seed plus all of them
-// (the same in every thread).  One barrier; the caller puts another one before s_w (WAVES * NL words) is reused.
-template <class Fr>
-__device__ __forceinline__ void block_scan_add(Fe<Fr> &mine, Fe<Fr> &total, const Fe<Fr> &g, const Fe<Fr> &seed, u32 *s_w)
-{
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    Fe<Fr> v = g;
-    wave_scan_add(v, lane);
-    if (lane == 63) lds_put(s_w + wave * NL, v.l);
-    __syncthreads();
-    Fe<Fr> y = seed, base = seed;
-#pragma unroll
-    for (int w = 0; w < WAVES; w++) {
-        Fe<Fr> t;
-        lds_get(t, s_w + w * NL);
-        add_canon(y, y, t);
-        if ((int)wave == w + 1) base = y;
-    }
-    total = y;
-    Fe<Fr> ex, sum;
-#pragma unroll
-    for (int i = 0; i < NL; i++) ex.l[i] = __shfl_up(v.l[i], 1, 64);
-    add_canon(sum, base, ex);
-    fe_select(mine, lane == 0, base, sum);
-}
-
-// RUN consecutive elements from index j0 of a vector of n, zero beyond n
-template <class Fr, int RUN>
-__device__ __forceinline__ void load_run_or_zero(Fe<Fr> (&x)[RUN], const u32 *vec, u64 j0, u64 n)
-{
-#pragma unroll
-    for (int e = 0; e < RUN; e++) {
-        if (j0 + e < n)
-            load_elem(x[e], vec + (j0 + e) * 8);
-        else
-            fe_zero(x[e]);
-    }
-}
-
-// launch 1: tt[blk] = the sum of tile a = blk % tiles of vector p = blk / tiles
-template <class Fr>
-__global__ void __launch_bounds__(THREADS) k_sum_totals(const u32 *__restrict__ in, u32 *__restrict__ tt, u64 n, unsigned tiles)
-{
-    __shared__ u32 s_w[WAVES * NL];
-    const unsigned blk = blockIdx.x, p = blk / tiles, a = blk - p * tiles;
-    Fe<Fr> x[E], g, zero, mine, total;
-    load_run_or_zero<Fr, E>(x, in + (u64)p * n * 8, (u64)a * TILE + threadIdx.x * E, n);
-    sum_run<Fr, E>(g, x);
-    fe_zero(zero);
-    block_scan_add(mine, total, g, zero, s_w);
-    if (threadIdx.x == 0) store_elem(tt + (u64)blk * 8, total);
-}
-
-// launch 2: one workgroup per vector.  SEEDS: the tile sums are replaced by their exclusive prefix sums, every thread storing the indices
-// it loaded.  values[p] = the vector's sum.
-template <class Fr, bool SEEDS>
-__global__ void __launch_bounds__(THREADS) k_sum_seeds(u32 *tt, u32 *__restrict__ values, unsigned tiles)
-{
-    __shared__ u32 s_w[WAVES * NL];
-    const unsigned p = blockIdx.x, chunks = (tiles + CHUNK - 1) / CHUNK;
-    u32 *T = tt + (u64)p * tiles * 8;
-    Fe<Fr> x[CE], g, s, carry, total;
-    fe_zero(carry);
-    for (unsigned k = 0; k < chunks; k++) {
-        const u64 a0 = (u64)k * CHUNK + threadIdx.x * CE;
-        load_run_or_zero<Fr, CE>(x, T, a0, tiles);
-        sum_run<Fr, CE>(g, x);
-        block_scan_add(s, total, g, carry, s_w);
-        carry = total;
-        if constexpr (SEEDS) {
-#pragma unroll
-            for (int e = 0; e < CE; e++) {
-                if (a0 + e < tiles) store_elem(T + (a0 + e) * 8, s);
-                if (e < CE - 1) add_canon(s, s, x[e]);
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) store_elem(values + (u64)p * 8, carry);
-}
-
-// launch 3: the outputs of tile a of vector p from the seed seeds[blk]
-template <class Fr>
-__global__ void __launch_bounds__(THREADS) k_sum_apply(const u32 *in, u32 *out, const u32 *__restrict__ seeds, u64 n, unsigned tiles)
-{
-    __shared__ u32 s_w[WAVES * NL];
-    const unsigned blk = blockIdx.x, p = blk / tiles, a = blk - p * tiles;
-    const u64 j0 = (u64)a * TILE + threadIdx.x * E;
-    Fe<Fr> x[E], g, seed, pre, total;
-    load_run_or_zero<Fr, E>(x, in + (u64)p * n * 8, j0, n);
-    sum_run<Fr, E>(g, x);
-    load_elem(seed, seeds + (u64)blk * 8);
-    block_scan_add(pre, total, g, seed, s_w);
-    u32 *dst = out + ((u64)p * n + j0) * 8;
-#pragma unroll
-    for (int e = 0; e < E; e++) {
-        if (j0 + e < n) store_elem(dst + e * 8, pre);
-        if (e < E - 1) add_canon(pre, pre, x[e]);
-    }
-}
-
-unsigned tiles_of(u64 n) { return (unsigned)((n + TILE - 1) / TILE); }
-
-template <class Fr>
-hipError_t call_running_sum(hipStream_t stream, const void *d_in, void *d_out, u64 n, unsigned batch, void *totals)
-{
-    const size_t bytes = (size_t)batch * n * 32;
-    if (panda::extent_too_short(d_in, bytes) || (d_out && panda::extent_too_short(d_out, bytes))) return hipErrorInvalidValue;
-    PANDA_TRY(panda::order_after_null_stream(stream));
-    const unsigned tiles = tiles_of(n);
-    const size_t tbytes = (size_t)batch * tiles * 32, vbytes = (size_t)batch * 32;
-    panda::Arena &arena = panda::thread_arena();
-    PANDA_TRY(arena.reserve(panda::align256(tbytes) + panda::align256(vbytes) + 512));
-    u32 *d_tt = (u32 *)arena.take(tbytes), *d_values = (u32 *)arena.take(vbytes);
-    if (!d_tt || !d_values) return hipErrorOutOfMemory;
-    hipLaunchKernelGGL((k_sum_totals<Fr>), dim3(batch * tiles), dim3(THREADS), 0, stream, (const u32 *)d_in, d_tt, n, tiles);
-    PANDA_TRY(hipGetLastError());
-    if (d_out) {
-        hipLaunchKernelGGL((k_sum_seeds<Fr, true>), dim3(batch), dim3(THREADS), 0, stream, d_tt, d_values, tiles);
-        PANDA_TRY(hipGetLastError());
-        hipLaunchKernelGGL((k_sum_apply<Fr>), dim3(batch * tiles), dim3(THREADS), 0, stream, (const u32 *)d_in, (u32 *)d_out, (const u32 *)d_tt, n, tiles);
-    } else
-        hipLaunchKernelGGL((k_sum_seeds<Fr, false>), dim3(batch), dim3(THREADS), 0, stream, d_tt, d_values, tiles);
-    PANDA_TRY(hipGetLastError());
-    if (totals) PANDA_TRY(hipMemcpyAsync(totals, d_values, vbytes, hipMemcpyDeviceToHost, stream));
-    return hipStreamSynchronize(stream);
-}
-
 } // namespace
 
 extern "C" {
@@ -390,11 +232,9 @@ panda_error panda_lookup_multiplicities(unsigned field, const void *d_table, uin
     for (unsigned c = 0; c < n_columns; c++)
         if (!columns[c] || ranges_overlap(d_mult, tbytes, columns[c], cbytes)) return panda_error_invalid_value;
     hipStream_t s = static_cast<hipStream_t>(stream.handle);
-    switch (field) {
-    case 0: return static_cast<panda_error>(call_multiplicities<Bn254Fr>(s, d_table, n_table, columns, n_columns, n, d_mult, missing, first_missing));
-    case 1: return static_cast<panda_error>(call_multiplicities<Bls377Fr>(s, d_table, n_table, columns, n_columns, n, d_mult, missing, first_missing));
-    default: return static_cast<panda_error>(call_multiplicities<Bls381Fr>(s, d_table, n_table, columns, n_columns, n, d_mult, missing, first_missing));
-    }
+    return with_field(field, [&](auto fr) {
+        return static_cast<panda_error>(call_multiplicities<decltype(fr)>(s, d_table, n_table, columns, n_columns, n, d_mult, missing, first_missing));
+    });
 }
 
 panda_error panda_lookup_plan(uint64_t n_table, unsigned n_columns, uint64_t n, unsigned *log_slots, size_t *scratch_bytes, unsigned *launches)
@@ -414,30 +254,6 @@ panda_error panda_lookup_home_slot(unsigned field, const void *elem, unsigned lo
     memcpy(w, elem, 32);
     hash_elem(w, h, fp);
     *slot = home_slot(h, log_slots);
-    return panda_success;
-}
-
-// The exclusive running sum: see include/panda_interface.h.  Every check but the extents comes before any runtime call.
-panda_error panda_poly_running_sum(unsigned field, const void *d_in, void *d_out, uint64_t n, unsigned batch, void *totals, panda_stream stream)
-{
-    if (field > 2 || shape_invalid(n, batch) || !d_in || (!d_out && !totals)) return panda_error_invalid_value;
-    const size_t bytes = (size_t)batch * n * 32;
-    if (d_out && d_out != d_in && ranges_overlap(d_in, bytes, d_out, bytes)) return panda_error_invalid_value;
-    hipStream_t s = static_cast<hipStream_t>(stream.handle);
-    switch (field) {
-    case 0: return static_cast<panda_error>(call_running_sum<Bn254Fr>(s, d_in, d_out, n, batch, totals));
-    case 1: return static_cast<panda_error>(call_running_sum<Bls377Fr>(s, d_in, d_out, n, batch, totals));
-    default: return static_cast<panda_error>(call_running_sum<Bls381Fr>(s, d_in, d_out, n, batch, totals));
-    }
-}
-
-panda_error panda_poly_running_sum_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *carry_chunk, unsigned *launches_scan, unsigned *launches_total)
-{
-    if (shape_invalid(n, batch)) return panda_error_invalid_value;
-    if (tile) *tile = TILE;
-    if (carry_chunk) *carry_chunk = CHUNK;
-    if (launches_scan) *launches_scan = 3;
-    if (launches_total) *launches_total = 2;
     return panda_success;
 }
 

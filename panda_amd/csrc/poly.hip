@@ -13,7 +13,9 @@
 //   launch 3  k_poly_apply    workgroup (p, a) loads its tile, rescans the per-thread aggregates seeded with C_a, and every thread runs
 //                             q_j = c_(j+1) + z q_(j+1) down from its own right edge.  A thread stores only what it has loaded itself and
 //                             what crosses workgroups comes from launches 1 and 2, so d_quot == d_coeffs is safe.
-// Coefficients beyond n read as zero, so ragged tails (n no multiple of E, 64 E, TILE; a short last chunk) take the same code.
+// Coefficients beyond n read as zero, so ragged tails (n no multiple of E, 64 E, TILE; a short last chunk) take the same code.  The
+// padded load is poly_scan.h's; the scan itself is this file's own: a recurrence with per-step multipliers handed over by value
+// (Ladder), not a scan of elements under one operation.
 //
 // Arithmetic: the multipliers of one call (z, z^(E 2^s), y, y^(CE 2^s)) are wave-uniform; they are derived on the host and handed
 // to the kernels by value as (w, floor(w R / p)) pairs for fe_mul_shoup<F, UNIFORM>.  The constant is the plain integer z, so
@@ -25,9 +27,10 @@
 #include "fe29.h"
 #include "panda_internal.h"
 #include "poly_elem.h"
+#include "poly_scan.h"
 
 using namespace panda29;
-using namespace panda_poly; // load_elem, store_elem, lds_put, lds_get, shape_invalid, ranges_overlap, wire_below_modulus
+using namespace panda_poly;
 
 namespace {
 
@@ -35,6 +38,12 @@ constexpr int E = 8;                    // coefficients per thread
 constexpr int CE = 4;                   // tile totals per thread of the carry kernel
 constexpr unsigned TILE = THREADS * E, CHUNK = THREADS * CE;
 constexpr int LADDER = 7;               // m^(RUN 2^s), s = 0 .. 6: six cross-lane steps and the wave's width
+
+// what a run reads beyond the end of its vector (poly_scan.h: load_run)
+struct PadZero {
+    template <class Fr>
+    static __device__ __forceinline__ void identity(Fe<Fr> &r) { fe_zero(r); }
+};
 
 // the multipliers of one launch: the step m of the recurrence and m^(RUN 2^s), RUN the elements a thread covers
 template <class Fr>
@@ -52,7 +61,7 @@ __device__ __forceinline__ void axpy(Fe<Fr> &v, const Fe<Fr> &t, const FeTw<Fr> 
     fe_add(v, v, pr);
 }
 
-// the value `d` lanes up, zero past the end of the wave
+// the value `d` lanes up, zero past the end of the wave (the select per limb: built on poly_scan.h's lane_shift k_poly_totals lost a wave)
 template <class Fr>
 __device__ __forceinline__ void lanes_up(Fe<Fr> &r, const Fe<Fr> &v, unsigned d, unsigned lane)
 {
@@ -138,16 +147,8 @@ __global__ void __launch_bounds__(THREADS) k_poly_totals(const u32 *__restrict__
     const unsigned blk = blockIdx.x, p = blk / tiles, a = blk - p * tiles;
     const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u64 j0 = (u64)a * TILE + threadIdx.x * E;
-    const u32 *src = c + ((u64)p * n + j0) * 8;
-    Fe<Fr> x[E];
-#pragma unroll
-    for (int e = 0; e < E; e++) {
-        if (j0 + e < n)
-            load_elem(x[e], src + e * 8);
-        else
-            fe_zero(x[e]);
-    }
-    Fe<Fr> g;
+    Fe<Fr> x[E], g;
+    load_run<PadZero, Fr, E>(x, c + (u64)p * n * 8, j0, n);
     run_horner<Fr, E>(g, x, L.m);
     wave_reduce(g, L, lane);
     if (lane == 0) lds_put(s_w + wave * NL, g.l);
@@ -178,15 +179,8 @@ __global__ void __launch_bounds__(THREADS) k_poly_carries(u32 *__restrict__ tota
     fe_zero(carry);
     for (unsigned k = (tiles + CHUNK - 1) / CHUNK; k-- > 0;) {
         const unsigned a0 = k * CHUNK + threadIdx.x * CE;
-        Fe<Fr> x[CE];
-#pragma unroll
-        for (int e = 0; e < CE; e++) {
-            if (a0 + e < tiles)
-                load_elem(x[e], T + (u64)(a0 + e) * 8);
-            else
-                fe_zero(x[e]);
-        }
-        Fe<Fr> s, total;
+        Fe<Fr> x[CE], s, total;
+        load_run<PadZero, Fr, CE>(x, T, a0, tiles);
         block_suffix_scan<Fr, CE>(s, total, x, carry, L, s_w);
         carry = total;
         fe_reduce_small_2p(carry); // keeps the value bounded over any number of chunks
@@ -213,17 +207,9 @@ __global__ void __launch_bounds__(THREADS) k_poly_apply(const u32 *c, u32 *q, co
     __shared__ u32 s_w[WAVES * NL];
     const unsigned blk = blockIdx.x, p = blk / tiles, a = blk - p * tiles;
     const u64 j0 = (u64)a * TILE + threadIdx.x * E;
-    const u32 *src = c + ((u64)p * n + j0) * 8;
     u32 *dst = q + ((u64)p * n + j0) * 8;
-    Fe<Fr> x[E];
-#pragma unroll
-    for (int e = 0; e < E; e++) {
-        if (j0 + e < n)
-            load_elem(x[e], src + e * 8);
-        else
-            fe_zero(x[e]);
-    }
-    Fe<Fr> edge, s, total;
+    Fe<Fr> x[E], edge, s, total;
+    load_run<PadZero, Fr, E>(x, c + (u64)p * n * 8, j0, n);
     load_elem(edge, carries + (u64)blk * 8);
     block_suffix_scan<Fr, E>(s, total, x, edge, L, s_w); // the barrier inside is behind every load of the workgroup
 #pragma unroll
@@ -259,24 +245,16 @@ bool point_valid(unsigned field, const void *pt)
 {
     u32 w[8];
     memcpy(w, pt, sizeof(w));
-    switch (field) {
-    case 0: return wire_below_modulus<Bn254Fr>(w);
-    case 1: return wire_below_modulus<Bls377Fr>(w);
-    default: return wire_below_modulus<Bls381Fr>(w);
-    }
+    return with_field(field, [&](auto fr) { return wire_below_modulus<decltype(fr)>(w); });
 }
 
-unsigned tiles_of(u64 n) { return (unsigned)((n + TILE - 1) / TILE); }
-
-// the per-call scratch of the calling host thread (its arena, released by panda_ntt_tear_down): tile totals and the values
-hipError_t take_scratch(u64 n, unsigned batch, unsigned n_values, u32 **d_totals, u32 **d_values)
+// tile totals and n_values values per polynomial
+hipError_t take_totals(u64 n, unsigned batch, unsigned n_values, u32 **d_totals, u32 **d_values)
 {
-    const size_t tbytes = (size_t)batch * tiles_of(n) * 32, vbytes = (size_t)batch * n_values * 32;
-    panda::Arena &arena = panda::thread_arena();
-    PANDA_TRY(arena.reserve(panda::align256(tbytes) + panda::align256(vbytes) + 512));
-    *d_totals = (u32 *)arena.take(tbytes);
-    *d_values = (u32 *)arena.take(vbytes);
-    return (*d_totals && *d_values) ? hipSuccess : hipErrorOutOfMemory;
+    void *block[2];
+    PANDA_TRY(take_scratch({(size_t)batch * tiles_of(n, TILE) * 32, (size_t)batch * n_values * 32}, block));
+    *d_totals = (u32 *)block[0], *d_values = (u32 *)block[1];
+    return hipSuccess;
 }
 
 // launches 1 and 2 for one point: the values land at d_values[p * vstride + voff]; with `carries` the totals become the carries
@@ -289,7 +267,7 @@ hipError_t sweep(hipStream_t stream, const u32 *d_coeffs, u64 n, unsigned batch,
     make_ladder<Fr>(lz, z, E, &y); // y = z^TILE
     Ladder<Fr> ly;
     make_ladder<Fr>(ly, y, CE, nullptr);
-    const unsigned tiles = tiles_of(n);
+    const unsigned tiles = tiles_of(n, TILE);
     hipLaunchKernelGGL(k_poly_totals<Fr>, dim3(batch * tiles), dim3(THREADS), 0, stream, d_coeffs, d_totals, n, tiles, lz);
     PANDA_TRY(hipGetLastError());
     if (carries)
@@ -305,7 +283,7 @@ hipError_t run_evaluate(hipStream_t stream, const void *d_coeffs, u64 n, unsigne
     if (panda::extent_too_short(d_coeffs, (size_t)batch * n * 32)) return hipErrorInvalidValue;
     PANDA_TRY(panda::order_after_null_stream(stream));
     u32 *d_totals = nullptr, *d_values = nullptr;
-    PANDA_TRY(take_scratch(n, batch, n_points, &d_totals, &d_values));
+    PANDA_TRY(take_totals(n, batch, n_points, &d_totals, &d_values));
     for (unsigned k = 0; k < n_points; k++) { // one sweep over the coefficients per point
         Ladder<Fr> lz;
         PANDA_TRY(sweep<Fr>(stream, (const u32 *)d_coeffs, n, batch, points + 8 * k, d_totals, d_values, n_points, k, false, lz));
@@ -321,10 +299,10 @@ hipError_t run_divide(hipStream_t stream, const void *d_coeffs, void *d_quot, u6
     if (panda::extent_too_short(d_coeffs, bytes) || panda::extent_too_short(d_quot, bytes)) return hipErrorInvalidValue;
     PANDA_TRY(panda::order_after_null_stream(stream));
     u32 *d_totals = nullptr, *d_values = nullptr;
-    PANDA_TRY(take_scratch(n, batch, 1, &d_totals, &d_values));
+    PANDA_TRY(take_totals(n, batch, 1, &d_totals, &d_values));
     Ladder<Fr> lz;
     PANDA_TRY(sweep<Fr>(stream, (const u32 *)d_coeffs, n, batch, point, d_totals, d_values, 1, 0, true, lz));
-    const unsigned tiles = tiles_of(n);
+    const unsigned tiles = tiles_of(n, TILE);
     hipLaunchKernelGGL(k_poly_apply<Fr>, dim3(batch * tiles), dim3(THREADS), 0, stream, (const u32 *)d_coeffs, (u32 *)d_quot, d_totals, n, tiles, lz);
     PANDA_TRY(hipGetLastError());
     if (remainders) PANDA_TRY(hipMemcpyAsync(remainders, d_values, (size_t)batch * 32, hipMemcpyDeviceToHost, stream));
@@ -343,11 +321,7 @@ panda_error panda_poly_evaluate(unsigned field, const void *d_coeffs, uint64_t n
     for (unsigned k = 0; k < n_points; k++)
         if (!point_valid(field, (const char *)points + 32 * k)) return panda_error_invalid_value;
     hipStream_t s = static_cast<hipStream_t>(stream.handle);
-    switch (field) {
-    case 0: return static_cast<panda_error>(run_evaluate<Bn254Fr>(s, d_coeffs, n, batch, (const u32 *)points, n_points, values));
-    case 1: return static_cast<panda_error>(run_evaluate<Bls377Fr>(s, d_coeffs, n, batch, (const u32 *)points, n_points, values));
-    default: return static_cast<panda_error>(run_evaluate<Bls381Fr>(s, d_coeffs, n, batch, (const u32 *)points, n_points, values));
-    }
+    return with_field(field, [&](auto fr) { return static_cast<panda_error>(run_evaluate<decltype(fr)>(s, d_coeffs, n, batch, (const u32 *)points, n_points, values)); });
 }
 
 // Division by X - z: see include/panda_interface.h.  Every check comes before any runtime call.
@@ -355,14 +329,9 @@ panda_error panda_poly_divide_linear(unsigned field, const void *d_coeffs, void 
                                      panda_stream stream)
 {
     if (field > 2 || shape_invalid(n, batch) || !d_coeffs || !d_quot || !point || !point_valid(field, point)) return panda_error_invalid_value;
-    const size_t bytes = (size_t)batch * n * 32;
-    if (d_quot != d_coeffs && ranges_overlap(d_coeffs, bytes, d_quot, bytes)) return panda_error_invalid_value;
+    if (bad_pair(d_coeffs, d_quot, (size_t)batch * n * 32)) return panda_error_invalid_value;
     hipStream_t s = static_cast<hipStream_t>(stream.handle);
-    switch (field) {
-    case 0: return static_cast<panda_error>(run_divide<Bn254Fr>(s, d_coeffs, d_quot, n, batch, (const u32 *)point, remainders));
-    case 1: return static_cast<panda_error>(run_divide<Bls377Fr>(s, d_coeffs, d_quot, n, batch, (const u32 *)point, remainders));
-    default: return static_cast<panda_error>(run_divide<Bls381Fr>(s, d_coeffs, d_quot, n, batch, (const u32 *)point, remainders));
-    }
+    return with_field(field, [&](auto fr) { return static_cast<panda_error>(run_divide<decltype(fr)>(s, d_coeffs, d_quot, n, batch, (const u32 *)point, remainders)); });
 }
 
 panda_error panda_poly_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *carry_chunk, unsigned *launches_evaluate, unsigned *launches_divide)

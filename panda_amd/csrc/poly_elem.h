@@ -1,10 +1,12 @@
-// poly_elem.h -- what poly.hip, poly_product.hip and poly_terms.hip share: the 32-byte element load / store, the LDS moves of a 9-limb
-// value and the shape, overlap and modulus checks of their entry points.
+// poly_elem.h -- what poly.hip, poly_product.hip, poly_sum.hip, poly_terms.hip and lookup.hip share: the 32-byte element load / store,
+// the LDS moves of a 9-limb value, and on the host the dispatch over the scalar field, the arena scratch of a call and the shape,
+// overlap and modulus checks of the entry points.  The workgroup scan over these elements is poly_scan.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include "fe29.h"
+#include "panda_internal.h"
 
 namespace panda_poly {
 
@@ -68,6 +70,33 @@ inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t 
 {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+// two ranges of the same length may be one range or disjoint
+inline bool bad_pair(const void *a, const void *b, size_t bytes) { return a != b && ranges_overlap(a, bytes, b, bytes); }
+
+// f(Fr()) with the scalar field's parameter type; the entry points refuse field > 2 before they get here
+template <class F>
+inline auto with_field(unsigned field, F &&f)
+{
+    switch (field) {
+    case 0: return f(panda29::Bn254Fr());
+    case 1: return f(panda29::Bls377Fr());
+    default: return f(panda29::Bls381Fr());
+    }
+}
+
+// the per-call scratch of the calling host thread (its arena, released by panda_ntt_tear_down): N blocks of the given sizes, each
+// aligned to 256 bytes.  A repeated call with the same sizes allocates nothing.
+template <int N>
+inline hipError_t take_scratch(const size_t (&bytes)[N], void *(&block)[N])
+{
+    size_t total = 256 * N;
+    for (int i = 0; i < N; i++) total += panda::align256(bytes[i]);
+    panda::Arena &arena = panda::thread_arena();
+    PANDA_TRY(arena.reserve(total));
+    for (int i = 0; i < N; i++)
+        if (!(block[i] = arena.take(bytes[i]))) return hipErrorOutOfMemory;
+    return hipSuccess;
 }
 
 } // namespace panda_poly

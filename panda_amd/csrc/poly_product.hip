@@ -5,8 +5,8 @@
 //   1 / x_i = (prod_{j < i} x_j) (prod_{j > i} x_j) / prod_all x          Z_i = (prod_{j < i} num_j) (prod_{j >= i} den_j) / prod_all den
 //
 // so every output is an exclusive prefix product times a suffix product times the inverse of the vector's grand product (Z_0 = 1 comes out
-// of the formula).  Reduce-then-scan over tiles of TILE = THREADS * E elements, the launch structure of poly.hip; no kernel waits for
-// another workgroup:
+// of the formula).  Reduce-then-scan over tiles of TILE = THREADS * E elements, the launch structure of poly.hip, on the workgroup scan of poly_scan.h
+// with the operation OpMul below; no kernel waits for another workgroup:
 //   launch 1  k_product_totals  workgroup (p, a) multiplies tile a of vector p down to one element per operand (two for the product call)
 //   launch 2  k_product_seeds   one workgroup per vector, CHUNK = THREADS * CE tile totals per step, three walks over the totals: the grand
 //                               denominator product, inverted ONCE and multiplied by the call's constant (below); from the last chunk down the
@@ -30,6 +30,7 @@
 #include "fe29.h"
 #include "panda_internal.h"
 #include "poly_elem.h"
+#include "poly_scan.h"
 
 using namespace panda29;
 using namespace panda_poly;
@@ -42,71 +43,35 @@ constexpr unsigned TILE = THREADS * E, CHUNK = THREADS * CE;
 
 enum Mode { INVERSE = 0, PRODUCT = 1, RUNNING = 2 }; // RUNNING: PRODUCT with d_den == NULL
 
-// inclusive product scan of the wave: lane l <- prod_{u <= l} v_u (REV: u >= l).  Six products per thread.
-template <class Fr, bool REV>
-__device__ __forceinline__ void wave_scan(Fe<Fr> &v, unsigned lane)
-{
+// poly_scan.h's operation: the field's product.  Every operand of every product is tight, < 2p (bounds above); the run is the plain chain.
+struct OpMul {
+    template <class Fr>
+    static __device__ __forceinline__ void identity(Fe<Fr> &r) { fe_one(r); }
+    template <class Fr>
+    static __device__ __forceinline__ void combine(Fe<Fr> &r, const Fe<Fr> &a, const Fe<Fr> &b) { fe_mul(r, a, b); }
+    template <class Fr, int RUN>
+    static __device__ __forceinline__ void run(Fe<Fr> &g, const Fe<Fr> (&x)[RUN])
+    {
+        g = x[0];
 #pragma unroll
-    for (int s = 0; s < 6; s++) {
-        const unsigned d = 1u << s;
-        Fe<Fr> t, pr;
-#pragma unroll
-        for (int i = 0; i < NL; i++) t.l[i] = REV ? __shfl_down(v.l[i], d, 64) : __shfl_up(v.l[i], d, 64);
-        fe_mul(pr, v, t);
-        const bool in = REV ? lane + d < 64 : lane >= d;
-        fe_select(v, in, pr, v);
+        for (int e = 1; e < RUN; e++) fe_mul(g, g, x[e]);
     }
-}
+};
 
-template <class Fr, int RUN>
-__device__ __forceinline__ void run_product(Fe<Fr> &g, const Fe<Fr> (&x)[RUN])
+// the run from index j0 of the denominators of vector p: loaded for PRODUCT; for RUNNING (den is NULL) `fill` below n and one beyond
+template <class Fr, int MODE>
+__device__ __forceinline__ void load_den(Fe<Fr> (&x)[E], const u32 *den, unsigned p, u64 j0, u64 n, const Fe<Fr> &fill)
 {
-    g = x[0];
+    if constexpr (MODE == PRODUCT)
+        load_run<OpMul, Fr, E>(x, den + (u64)p * n * 8, j0, n);
+    else {
 #pragma unroll
-    for (int e = 1; e < RUN; e++) fe_mul(g, g, x[e]);
-}
-
-// g is the product of the calling thread's run.  mine <- seed times the g of every thread before the caller (REV: behind it), total <-
-// seed times all of them (the same in every thread).  One barrier; the caller puts another one before s_w (WAVES * NL words) is reused.
-// Products per thread: 6 (wave scan) + WAVES (across the waves) + 1.
-template <class Fr, bool REV>
-__device__ __forceinline__ void block_scan(Fe<Fr> &mine, Fe<Fr> &total, const Fe<Fr> &g, const Fe<Fr> &seed, u32 *s_w)
-{
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    Fe<Fr> v = g;
-    wave_scan<Fr, REV>(v, lane);
-    if (lane == (REV ? 0u : 63u)) lds_put(s_w + wave * NL, v.l);
-    __syncthreads();
-    Fe<Fr> y = seed, base = seed;
-#pragma unroll
-    for (int k = 0; k < WAVES; k++) {
-        const int w = REV ? WAVES - 1 - k : k;
-        Fe<Fr> t;
-        lds_get(t, s_w + w * NL);
-        fe_mul(y, y, t);
-        if ((int)wave == (REV ? w - 1 : w + 1)) base = y;
-    }
-    total = y;
-    Fe<Fr> ex, pr;
-#pragma unroll
-    for (int i = 0; i < NL; i++) ex.l[i] = REV ? __shfl_down(v.l[i], 1, 64) : __shfl_up(v.l[i], 1, 64);
-    fe_mul(pr, base, ex);
-    fe_select(mine, lane == (REV ? 63u : 0u), base, pr);
-}
-
-// RUN consecutive elements from index j0 of a vector of n, one beyond n; `fill`: every element in range is this value instead
-template <class Fr, int RUN>
-__device__ __forceinline__ void load_run(Fe<Fr> (&x)[RUN], const u32 *vec, u64 j0, u64 n, const Fe<Fr> *fill = nullptr)
-{
-#pragma unroll
-    for (int e = 0; e < RUN; e++) {
-        if (j0 + e < n) {
-            if (fill)
-                x[e] = *fill;
+        for (int e = 0; e < E; e++) {
+            if (j0 + e < n)
+                x[e] = fill;
             else
-                load_elem(x[e], vec + (j0 + e) * 8);
-        } else
-            fe_one(x[e]);
+                fe_one(x[e]);
+        }
     }
 }
 
@@ -126,25 +91,6 @@ __device__ __forceinline__ unsigned mask_zeros(Fe<Fr> (&x)[RUN])
     return mask;
 }
 
-// the product of the workgroup's 256 run products, valid in thread 0
-template <class Fr>
-__device__ __forceinline__ void block_product(Fe<Fr> &g, u32 *s_w)
-{
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    wave_scan<Fr, false>(g, lane);
-    if (lane == 63) lds_put(s_w + wave * NL, g.l);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        lds_get(g, s_w);
-#pragma unroll
-        for (int w = 1; w < WAVES; w++) {
-            Fe<Fr> t;
-            lds_get(t, s_w + w * NL);
-            fe_mul(g, g, t);
-        }
-    }
-}
-
 // launch 1: tn[blk] (and td[blk], but for INVERSE) = the product of tile a = blk % tiles of vector p = blk / tiles
 template <class Fr, int MODE>
 __global__ void __launch_bounds__(THREADS) k_product_totals(const u32 *__restrict__ num, const u32 *__restrict__ den, u32 *__restrict__ tn, u32 *__restrict__ td, u64 n,
@@ -154,15 +100,15 @@ __global__ void __launch_bounds__(THREADS) k_product_totals(const u32 *__restric
     const unsigned blk = blockIdx.x, p = blk / tiles, a = blk - p * tiles;
     const u64 j0 = (u64)a * TILE + threadIdx.x * E;
     Fe<Fr> x[E], g;
-    load_run<Fr, E>(x, num + (u64)p * n * 8, j0, n);
+    load_run<OpMul, Fr, E>(x, num + (u64)p * n * 8, j0, n);
     if constexpr (MODE == INVERSE) mask_zeros<Fr, E>(x);
-    run_product<Fr, E>(g, x);
-    block_product(g, s_w);
+    OpMul::run(g, x);
+    block_reduce<OpMul>(g, s_w);
     if (threadIdx.x == 0) store_elem(tn + (u64)blk * 8, g);
     if constexpr (MODE != INVERSE) {
-        load_run<Fr, E>(x, MODE == PRODUCT ? den + (u64)p * n * 8 : nullptr, j0, n, MODE == PRODUCT ? nullptr : &fill);
-        run_product<Fr, E>(g, x);
-        block_product(g, s_w + WAVES * NL);
+        load_den<Fr, MODE>(x, den, p, j0, n, fill);
+        OpMul::run(g, x);
+        block_reduce<OpMul>(g, s_w + WAVES * NL);
         if (threadIdx.x == 0) store_elem(td + (u64)blk * 8, g);
     }
 }
@@ -173,29 +119,24 @@ template <class Fr, bool INV>
 __global__ void __launch_bounds__(THREADS) k_product_seeds(u32 *tn, u32 *td, u32 *__restrict__ values, unsigned tiles, Fe<Fr> fold)
 {
     __shared__ u32 s_w[WAVES * NL];
-    const unsigned p = blockIdx.x, chunks = (tiles + CHUNK - 1) / CHUNK;
+    const unsigned p = blockIdx.x;
     u32 *N = tn + (u64)p * tiles * 8, *D = td + (u64)p * tiles * 8;
     const u32 *Din = INV ? N : D;
-    Fe<Fr> x[CE], g, s, carry, total;
+    Fe<Fr> carry, inv;
     // the grand product of the denominator totals and its inverse
     fe_one(carry);
-    for (unsigned k = 0; k < chunks; k++) {
-        load_run<Fr, CE>(x, Din, (u64)k * CHUNK + threadIdx.x * CE, tiles);
-        run_product<Fr, CE>(g, x);
-        block_scan<Fr, false>(s, total, g, carry, s_w);
-        carry = total;
-        __syncthreads();
-    }
-    Fe<Fr> inv;
+    walk_totals<OpMul, Fr, CE, false>(carry, Din, nullptr, tiles, s_w);
     fe_inv(inv, carry); // zero for zero
     fe_mul(inv, inv, fold);
-    // suffix seeds, from the last chunk down: D_a = inv * prod_{b > a} den total b
+    // suffix seeds, from the last chunk down: D_a = inv * prod_{b > a} den total b.  walk_totals' steps the other way round, spelled out:
+    // through a REV parameter of that function this kernel's INV form came out at five waves per SIMD instead of four.
     carry = inv;
-    for (unsigned k = chunks; k-- > 0;) {
+    for (unsigned k = tiles_of(tiles, CHUNK); k-- > 0;) {
         const u64 a0 = (u64)k * CHUNK + threadIdx.x * CE;
-        load_run<Fr, CE>(x, Din, a0, tiles);
-        run_product<Fr, CE>(g, x);
-        block_scan<Fr, true>(s, total, g, carry, s_w);
+        Fe<Fr> x[CE], g, s, total;
+        load_run<OpMul, Fr, CE>(x, Din, a0, tiles);
+        OpMul::run(g, x);
+        block_scan<OpMul, Fr, true>(s, total, g, carry, s_w);
         carry = total;
 #pragma unroll
         for (int e = CE - 1; e >= 0; e--) {
@@ -206,19 +147,7 @@ __global__ void __launch_bounds__(THREADS) k_product_seeds(u32 *tn, u32 *td, u32
     }
     // prefix seeds, from the first chunk up: N_a = prod_{b < a} num total b
     fe_one(carry);
-    for (unsigned k = 0; k < chunks; k++) {
-        const u64 a0 = (u64)k * CHUNK + threadIdx.x * CE;
-        load_run<Fr, CE>(x, N, a0, tiles);
-        run_product<Fr, CE>(g, x);
-        block_scan<Fr, false>(s, total, g, carry, s_w);
-        carry = total;
-#pragma unroll
-        for (int e = 0; e < CE; e++) {
-            if (a0 + e < tiles) store_elem(N + (a0 + e) * 8, s);
-            if (e < CE - 1) fe_mul(s, s, x[e]);
-        }
-        __syncthreads();
-    }
+    walk_totals<OpMul, Fr, CE, true>(carry, N, N, tiles, s_w);
     if constexpr (!INV) {
         if (threadIdx.x == 0) {
             fe_mul(carry, carry, inv);
@@ -237,23 +166,23 @@ __global__ void __launch_bounds__(THREADS) k_product_apply(const u32 *num, const
     const u64 j0 = (u64)a * TILE + threadIdx.x * E;
     Fe<Fr> x[E], d[E], gn, gd;
     unsigned zeros = 0;
-    load_run<Fr, E>(x, num + (u64)p * n * 8, j0, n);
+    load_run<OpMul, Fr, E>(x, num + (u64)p * n * 8, j0, n);
     if constexpr (MODE == INVERSE) {
         zeros = mask_zeros<Fr, E>(x);
 #pragma unroll
         for (int e = 0; e < E; e++) d[e] = x[e];
     } else
-        load_run<Fr, E>(d, MODE == PRODUCT ? den + (u64)p * n * 8 : nullptr, j0, n, MODE == PRODUCT ? nullptr : &fill);
-    run_product<Fr, E>(gn, x);
+        load_den<Fr, MODE>(d, den, p, j0, n, fill);
+    OpMul::run(gn, x);
     if constexpr (MODE == INVERSE)
         gd = gn;
     else
-        run_product<Fr, E>(gd, d);
+        OpMul::run(gd, d);
     Fe<Fr> seed_n, seed_d, pre, suf, total;
     load_elem(seed_n, sn + (u64)blk * 8);
     load_elem(seed_d, sd + (u64)blk * 8);
-    block_scan<Fr, false>(pre, total, gn, seed_n, s_w);
-    block_scan<Fr, true>(suf, total, gd, seed_d, s_w + WAVES * NL);
+    block_scan<OpMul, Fr, false>(pre, total, gn, seed_n, s_w);
+    block_scan<OpMul, Fr, true>(suf, total, gd, seed_d, s_w + WAVES * NL);
     // x[e] <- the exclusive prefix product at element e
 #pragma unroll
     for (int e = 0; e < E; e++) {
@@ -278,18 +207,14 @@ __global__ void __launch_bounds__(THREADS) k_product_apply(const u32 *num, const
 
 // ------------------------------------------------------------------------------- host side
 
-unsigned tiles_of(u64 n) { return (unsigned)((n + TILE - 1) / TILE); }
-
-// the per-call scratch of the calling host thread (its arena, released by panda_ntt_tear_down): two totals per tile and a value per vector
-hipError_t take_scratch(u64 n, unsigned batch, u32 **d_tn, u32 **d_td, u32 **d_values)
+// two totals per tile and a value per vector
+hipError_t take_totals(u64 n, unsigned batch, u32 **d_tn, u32 **d_td, u32 **d_values)
 {
-    const size_t tbytes = (size_t)batch * tiles_of(n) * 32, vbytes = (size_t)batch * 32;
-    panda::Arena &arena = panda::thread_arena();
-    PANDA_TRY(arena.reserve(2 * panda::align256(tbytes) + panda::align256(vbytes) + 768));
-    *d_tn = (u32 *)arena.take(tbytes);
-    *d_td = (u32 *)arena.take(tbytes);
-    *d_values = (u32 *)arena.take(vbytes);
-    return (*d_tn && *d_td && *d_values) ? hipSuccess : hipErrorOutOfMemory;
+    const size_t tbytes = (size_t)batch * tiles_of(n, TILE) * 32;
+    void *block[3];
+    PANDA_TRY(take_scratch({tbytes, tbytes, (size_t)batch * 32}, block));
+    *d_tn = (u32 *)block[0], *d_td = (u32 *)block[1], *d_values = (u32 *)block[2];
+    return hipSuccess;
 }
 
 // the wire's one as the kernels hold it: the integer W mod p, which is c = W / R in the form fe_mul multiplies
@@ -312,7 +237,7 @@ hipError_t launch_all(hipStream_t stream, const u32 *d_num, const u32 *d_den, u3
         fe_mul(fold, c, c); // c^2
     else
         fold = c;
-    const unsigned tiles = tiles_of(n);
+    const unsigned tiles = tiles_of(n, TILE);
     hipLaunchKernelGGL((k_product_totals<Fr, MODE>), dim3(batch * tiles), dim3(THREADS), 0, stream, d_num, d_den, d_tn, d_td, n, tiles, c);
     PANDA_TRY(hipGetLastError());
     hipLaunchKernelGGL((k_product_seeds<Fr, MODE == INVERSE>), dim3(batch), dim3(THREADS), 0, stream, d_tn, d_td, d_values, tiles, fold);
@@ -328,7 +253,7 @@ hipError_t call_inverse(hipStream_t stream, const void *d_in, void *d_out, u64 n
     if (panda::extent_too_short(d_in, bytes) || panda::extent_too_short(d_out, bytes)) return hipErrorInvalidValue;
     PANDA_TRY(panda::order_after_null_stream(stream));
     u32 *d_tn = nullptr, *d_td = nullptr, *d_values = nullptr;
-    PANDA_TRY(take_scratch(n, 1, &d_tn, &d_td, &d_values));
+    PANDA_TRY(take_totals(n, 1, &d_tn, &d_td, &d_values));
     PANDA_TRY((launch_all<Fr, INVERSE>(stream, (const u32 *)d_in, nullptr, (u32 *)d_out, n, 1, d_tn, d_td, d_values)));
     return hipStreamSynchronize(stream);
 }
@@ -340,7 +265,7 @@ hipError_t call_product(hipStream_t stream, const void *d_num, const void *d_den
     if (panda::extent_too_short(d_num, bytes) || (d_den && panda::extent_too_short(d_den, bytes)) || panda::extent_too_short(d_out, bytes)) return hipErrorInvalidValue;
     PANDA_TRY(panda::order_after_null_stream(stream));
     u32 *d_tn = nullptr, *d_td = nullptr, *d_values = nullptr;
-    PANDA_TRY(take_scratch(n, batch, &d_tn, &d_td, &d_values));
+    PANDA_TRY(take_totals(n, batch, &d_tn, &d_td, &d_values));
     if (d_den)
         PANDA_TRY((launch_all<Fr, PRODUCT>(stream, (const u32 *)d_num, (const u32 *)d_den, (u32 *)d_out, n, batch, d_tn, d_td, d_values)));
     else
@@ -348,9 +273,6 @@ hipError_t call_product(hipStream_t stream, const void *d_num, const void *d_den
     if (totals) PANDA_TRY(hipMemcpyAsync(totals, d_values, (size_t)batch * 32, hipMemcpyDeviceToHost, stream));
     return hipStreamSynchronize(stream);
 }
-
-// two ranges of the same length may be one range or disjoint
-bool bad_pair(const void *a, const void *b, size_t bytes) { return a != b && ranges_overlap(a, bytes, b, bytes); }
 
 } // namespace
 
@@ -361,11 +283,7 @@ panda_error panda_field_batch_inverse(unsigned field, const void *d_in, void *d_
 {
     if (field > 2 || shape_invalid(n, 1) || !d_in || !d_out || bad_pair(d_in, d_out, (size_t)n * 32)) return panda_error_invalid_value;
     hipStream_t s = static_cast<hipStream_t>(stream.handle);
-    switch (field) {
-    case 0: return static_cast<panda_error>(call_inverse<Bn254Fr>(s, d_in, d_out, n));
-    case 1: return static_cast<panda_error>(call_inverse<Bls377Fr>(s, d_in, d_out, n));
-    default: return static_cast<panda_error>(call_inverse<Bls381Fr>(s, d_in, d_out, n));
-    }
+    return with_field(field, [&](auto fr) { return static_cast<panda_error>(call_inverse<decltype(fr)>(s, d_in, d_out, n)); });
 }
 
 // The running product of num / den: see include/panda_interface.h.  Every check comes before any runtime call.
@@ -375,11 +293,7 @@ panda_error panda_poly_grand_product(unsigned field, const void *d_num, const vo
     const size_t bytes = (size_t)batch * n * 32;
     if (bad_pair(d_num, d_out, bytes) || (d_den && (bad_pair(d_den, d_out, bytes) || bad_pair(d_num, d_den, bytes)))) return panda_error_invalid_value;
     hipStream_t s = static_cast<hipStream_t>(stream.handle);
-    switch (field) {
-    case 0: return static_cast<panda_error>(call_product<Bn254Fr>(s, d_num, d_den, d_out, n, batch, totals));
-    case 1: return static_cast<panda_error>(call_product<Bls377Fr>(s, d_num, d_den, d_out, n, batch, totals));
-    default: return static_cast<panda_error>(call_product<Bls381Fr>(s, d_num, d_den, d_out, n, batch, totals));
-    }
+    return with_field(field, [&](auto fr) { return static_cast<panda_error>(call_product<decltype(fr)>(s, d_num, d_den, d_out, n, batch, totals)); });
 }
 
 panda_error panda_poly_product_plan(uint64_t n, unsigned batch, unsigned *tile_inverse, unsigned *tile_product, unsigned *carry_chunk, unsigned *launches)

@@ -14,6 +14,7 @@
 #include "fe29.h"
 #include "panda_internal.h"
 #include "poly_elem.h"
+#include "poly_scan.h"
 #include "poly_terms.h"
 
 using namespace panda29;
@@ -111,20 +112,7 @@ bool arguments_valid(unsigned field, const panda_sop_expression *x, const void *
     }
     for (unsigned f = 0; f < total; f++)
         if (in_place[x->factors[f].column] && panda_sop::reduce_rotation(x->factors[f].rotation, n) != 0) return false;
-    switch (field) {
-    case 0: return constants_valid<Bn254Fr>(*x);
-    case 1: return constants_valid<Bls377Fr>(*x);
-    default: return constants_valid<Bls381Fr>(*x);
-    }
-}
-
-// the per-call scratch of the calling host thread (its arena, released by panda_ntt_tear_down): the program
-hipError_t take_scratch(Program **d_prog)
-{
-    panda::Arena &arena = panda::thread_arena();
-    PANDA_TRY(arena.reserve(panda::align256(sizeof(Program)) + 256));
-    *d_prog = (Program *)arena.take(sizeof(Program));
-    return *d_prog ? hipSuccess : hipErrorOutOfMemory;
+    return with_field(field, [&](auto fr) { return constants_valid<decltype(fr)>(*x); });
 }
 
 template <class Fr>
@@ -135,12 +123,13 @@ hipError_t run(hipStream_t stream, const panda_sop_expression &x, void *d_out, u
     for (unsigned c = 0; c < x.n_columns; c++)
         if (panda::extent_too_short(x.columns[c], bytes)) return hipErrorInvalidValue;
     PANDA_TRY(panda::order_after_null_stream(stream));
-    Program *d_prog = nullptr;
-    PANDA_TRY(take_scratch(&d_prog));
+    void *block[1]; // the program
+    PANDA_TRY(take_scratch({sizeof(Program)}, block));
+    Program *d_prog = (Program *)block[0];
     Program prog; // lives until the synchronise below
     panda_sop::build_program<Fr>(prog, x.columns, x.n_columns, x.coeffs, x.degrees, x.n_terms, x.factors, x.scales, x.n_scales, x.scale_mode, n);
     PANDA_TRY(hipMemcpyAsync(d_prog, &prog, sizeof(Program), hipMemcpyHostToDevice, stream));
-    const unsigned tiles = (unsigned)((n + TILE - 1) / TILE);
+    const unsigned tiles = tiles_of(n, TILE);
     hipLaunchKernelGGL(k_sum_of_products<Fr>, dim3(batch * tiles), dim3(THREADS), 0, stream, (const Program *)d_prog, (u32 *)d_out, (u32)n, tiles);
     PANDA_TRY(hipGetLastError());
     return hipStreamSynchronize(stream);
@@ -155,11 +144,7 @@ panda_error panda_poly_sum_of_products(unsigned field, const panda_sop_expressio
 {
     if (!arguments_valid(field, expr, d_out, n, batch)) return panda_error_invalid_value;
     hipStream_t s = static_cast<hipStream_t>(stream.handle);
-    switch (field) {
-    case 0: return static_cast<panda_error>(run<Bn254Fr>(s, *expr, d_out, n, batch));
-    case 1: return static_cast<panda_error>(run<Bls377Fr>(s, *expr, d_out, n, batch));
-    default: return static_cast<panda_error>(run<Bls381Fr>(s, *expr, d_out, n, batch));
-    }
+    return with_field(field, [&](auto fr) { return static_cast<panda_error>(run<decltype(fr)>(s, *expr, d_out, n, batch)); });
 }
 
 panda_error panda_poly_sum_of_products_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *launches)

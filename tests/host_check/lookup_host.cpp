@@ -1,5 +1,5 @@
-// Host run of what panda_amd/csrc/lookup.h shares between the kernels of lookup.hip and the host, built with FE29_CHECK (128-bit shadow
-// column accumulators in fe_mul, the limb-range assertion of fe_carry):
+// Host run of what panda_amd/csrc/lookup.h and poly_sum.h share between the kernels of lookup.hip and poly_sum.hip and the host, built
+// with FE29_CHECK (128-bit shadow column accumulators in fe_mul, the limb-range assertion of fe_carry):
 //   * the hash: `lookup_host hash <log_slots> <64 hex digits, the 32 bytes of an element in memory order> ...` prints the home slot of
 //     every element, which the test compares with panda_lookup_home_slot;
 //   * without arguments: the count -> wire conversion for the counts 0, 1, 2^28 - 1, 2^28 and the running sum's addition chains at
@@ -12,9 +12,11 @@
 #include <string.h>
 
 #include "../../panda_amd/csrc/lookup.h"
+#include "../../panda_amd/csrc/poly_sum.h"
 
 using namespace panda29;
 using namespace panda_lookup;
+using namespace panda_poly;
 
 namespace {
 

@@ -62,7 +62,7 @@ def wave_scan(v, sh, rev):
 
 
 def block_scan(sh, g, seed, rev):
-    """block_scan of csrc/poly_product.hip: g (threads,) -> (seed times the g of every thread before (rev: behind) each thread, seed times all)"""
+    """block_scan of csrc/poly_scan.h with the product: g (threads,) -> (seed times the g of every thread before (rev: behind) each thread, seed times all)"""
     v = wave_scan(g.reshape(sh.waves, sh.wave), sh, rev)
     wave_total = v[:, 0] if rev else v[:, -1]
     base = np.zeros(sh.waves, np.int64)
