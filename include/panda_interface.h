@@ -14,7 +14,7 @@
  * (binding.rs:14,16,54-56).  Part 3 is additive (no reference counterpart): BLS12-377 / BLS12-381 / BN254 G2 / BLS12-381 G2 / BLS12-377 G2,
  * cached-base registration and tables, the in-call upload pipeline, inverse / coset / bit-reversed NTTs, batches, the low-degree
  * extension, polynomial evaluation and division by X - z, batch inversion and grand products over the scalar fields, fused sums of
- * products, logUp lookup support (multiplicities and running sums), multi-GPU halves and
+ * products, logUp lookup support (multiplicities and running sums), sumcheck rounds over multilinear tables, multi-GPU halves and
  * synthetic-input / diagnostics entry points.
  *
  * Conventions (unchanged from the reference):
@@ -532,6 +532,66 @@ panda_error panda_poly_running_sum(unsigned field, const void *d_in, void *d_out
  * second level takes per step, *launches_scan / *launches_total = the kernel launches with and without d_out (3, 2).  None depends on
  * `batch`.  Any pointer may be NULL.  Invalid for the shapes the execute call refuses (n == 0, batch == 0, n or batch x n > 2^28). */
 panda_error panda_poly_running_sum_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *carry_chunk, unsigned *launches_scan, unsigned *launches_total);
+/* Sumcheck over multilinear tables -- the round of HyperPlonk, Spartan, GKR, Lasso / Jolt and every zerocheck.  A table is 2^log_n
+ * elements f[x], the values of a multilinear polynomial at the bits of x, in the 32-byte canonical Montgomery wire form of every other
+ * call (field: 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr); a non-canonical input is outside the contract.  A round binds one variable:
+ *   PANDA_MLE_BIND_LOW   pair i < 2^(log_n - 1) is lo = f[2i], hi = f[2i + 1]            (arkworks fix_variables, HyperPlonk)
+ *   PANDA_MLE_BIND_HIGH  pair i is lo = f[i], hi = f[i + 2^(log_n - 1)]                  (Spartan, Jolt, Lasso)
+ *   fold with r:         F[i] = lo + r (hi - lo), 2^(log_n - 1) elements
+ *   round polynomial:    g(t) = sum_i sum_terms coeff_term prod_{f < degree_term} ( lo_{c_f, i} + t (hi_{c_f, i} - lo_{c_f, i}) )
+ * for t = 0 .. n_evals - 1, over the terms of a panda_sop_expression, the grammar of panda_poly_sum_of_products.
+ *
+ * panda_sumcheck_round.  expr: the columns are tables of 2^log_n elements (one vector each); every rotation must be 0 and scale_mode
+ * PANDA_SOP_SCALE_NONE; the caps on columns, terms and factors are those of the sum of products.  n_evals in 1 ..
+ * PANDA_SUMCHECK_MAX_EVALS: the caller asks for degree + 1 points, the library does not second-guess it.  evals[t] (HOST, n_evals x 32 B) =
+ * g(t), canonical; field addition is exact, so the bytes are the same on every run whatever the order of the sums.
+ *   challenge == NULL and folded == NULL: g over the tables as they stand, 2^(log_n - 1) pairs; log_n in 1 .. 28.  The columns are read
+ *     only and may be equal to or overlap each other freely.
+ *   challenge (HOST, 32 B, below the modulus) and folded (HOST array of n_columns DEVICE pointers, 2^(log_n - 1) elements each) both
+ *     given, the FUSED round: every column is first folded with the challenge, in `order`, into folded[c], and g is taken over the folded
+ *     tables, 2^(log_n - 2) pairs; log_n in 2 .. 28.  One pass: a thread reads the four source elements of a pair of folded elements,
+ *     stores the two folded elements and evaluates from registers; nothing folded is read back.  Every column is folded, whether a
+ *     factor names it or not.  Exactly one of the two pointers NULL is refused.
+ *   A k-variable sumcheck is one plain round, k - 1 fused rounds (each with the challenge of the round before, log_n falling by one),
+ *     and one panda_mle_fold on the 2-element tables, which gives the final evaluations.
+ *   Aliasing (fused round and panda_mle_fold alike).  The folded ranges must be pairwise disjoint.  folded[c] == columns[c] exactly is in
+ *     place, legal with PANDA_MLE_BIND_HIGH alone and only if columns[c] overlaps no other column: the thread of output i reads f[i] and
+ *     f[i + half] and writes F[i] after it has read them, so it writes only bytes no other thread reads.  With PANDA_MLE_BIND_LOW output
+ *     i lies where the thread of output i / 2 reads: in place is refused, as is every other overlap of a folded range with a column.
+ *   Synchronous on return.  Two kernel launches (a sum per point and workgroup; one workgroup per point over those sums); no kernel waits
+ *     for another workgroup, no atomics.  The program (about 7 KB) and n_evals x tiles x 32 bytes of sums go to the calling host
+ *     thread's arena scratch: a repeated call allocates nothing, panda_ntt_tear_down releases it.  Bytes behind a folded table are never
+ *     written.
+ *   panda_error_invalid_value, nothing launched, no output written: field > 2, log_n outside the ranges above, order > 1, n_evals 0 or >
+ *     PANDA_SUMCHECK_MAX_EVALS, NULL expr / evals / columns / coeffs / degrees, a NULL column or folded pointer, exactly one of challenge /
+ *     folded NULL, the expression errors of panda_poly_sum_of_products (counts, a factor's column index), a rotation other than 0, a
+ *     scale mode other than NONE, a coefficient or the challenge >= the modulus, the overlaps above (all checked before any runtime
+ *     call), and buffers of this library's allocators shorter than stated.
+ *
+ * panda_mle_fold: the fold alone, folded[c][i] = lo + challenge (hi - lo) for all n_columns (1 .. PANDA_SOP_MAX_COLUMNS) tables in ONE
+ * launch; log_n in 1 .. 28.  The last step of a sumcheck, and the unfused arm of a round.  Aliasing, refusals and synchronisation as above
+ * (NULL columns / folded / challenge are refused).
+ *
+ * panda_mle_eq_table: d_out[x] = prod_{j < log_n} ( x_j r_j + (1 - x_j)(1 - r_j) ) for x < 2^log_n, x_j bit j of x and r_j = point[j]
+ * (HOST, log_n x 32 B, each below the modulus) -- the table a zerocheck multiplies its gate by, and the weights of a multilinear
+ * evaluation: sum_x f(x) eq(r, x) is g(0) + g(1) of the term f eq.  log_n in 0 .. 28; log_n = 0 writes the wire's one (point is then not
+ * read but must not be NULL).  Canonical output, one launch, synchronous; the factors (about 2 KB) go to the arena scratch.  Refused:
+ * field > 2, log_n > 28, NULL point / d_out, a coordinate >= the modulus, a d_out of this library's allocators shorter than stated.
+ *
+ * panda_sumcheck_plan (pure host arithmetic, no device call): *tile_pairs = the pairs one workgroup of the round kernel covers (`fused`
+ * 0 / 1 selects the kernel), *carry_chunk = the tile sums the second level takes per step, *launches = the kernel launches of a round
+ * (2).  Any pointer may be NULL.  Invalid for the shapes the round refuses: fused > 1, log_n < 1 + fused or > 28, n_evals 0 or above the
+ * cap. */
+#define PANDA_MLE_BIND_LOW  0u
+#define PANDA_MLE_BIND_HIGH 1u
+#define PANDA_SUMCHECK_MAX_EVALS 8   /* t = 0..7: degree 7, a degree-5 custom gate times eq fits */
+panda_error panda_sumcheck_round(unsigned field, const panda_sop_expression *expr, unsigned log_n, unsigned order, unsigned n_evals,
+                                 const void *challenge /* HOST 32 B, or NULL */, void *const *folded /* HOST array of n_columns DEVICE pointers, or NULL */,
+                                 void *evals /* HOST, n_evals x 32 B */, panda_stream stream);
+panda_error panda_mle_fold(unsigned field, const void *const *columns, void *const *folded, unsigned n_columns, unsigned log_n, unsigned order,
+                           const void *challenge /* HOST 32 B */, panda_stream stream);
+panda_error panda_mle_eq_table(unsigned field, const void *point /* HOST, log_n x 32 B */, unsigned log_n, void *d_out /* DEVICE 2^log_n x 32 B */, panda_stream stream);
+panda_error panda_sumcheck_plan(unsigned log_n, unsigned fused, unsigned n_evals, unsigned *tile_pairs, unsigned *carry_chunk, unsigned *launches);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

@@ -69,6 +69,9 @@ POLY_MAX_POINTS = 8  # PANDA_POLY_MAX_POINTS
 SOP_MAX_COLUMNS, SOP_MAX_TERMS, SOP_MAX_FACTORS, SOP_MAX_SCALES = 32, 64, 256, 16
 SOP_SCALE_NONE, SOP_SCALE_PER_VECTOR, SOP_SCALE_CYCLIC = 0, 1, 2
 LOOKUP_MAX_COLUMNS = 32  # PANDA_LOOKUP_MAX_COLUMNS
+# panda_sumcheck_round / panda_mle_fold: the binding orders (PANDA_MLE_BIND_*) and the most evaluation points of a round polynomial
+MLE_BIND_LOW, MLE_BIND_HIGH = 0, 1
+SUMCHECK_MAX_EVALS = 8  # PANDA_SUMCHECK_MAX_EVALS
 CLOCK_WORDS, CLOCK_STAMP_BYTES = 12, 32768  # PANDA_CLOCK_WORDS, PANDA_CLOCK_STAMP_BYTES
 
 
@@ -122,6 +125,7 @@ ADDITIVE_SYMBOLS = [
     "panda_field_batch_inverse", "panda_poly_grand_product", "panda_poly_product_plan",
     "panda_poly_sum_of_products", "panda_poly_sum_of_products_plan",
     "panda_lookup_multiplicities", "panda_lookup_plan", "panda_lookup_home_slot", "panda_poly_running_sum", "panda_poly_running_sum_plan",
+    "panda_sumcheck_round", "panda_mle_fold", "panda_mle_eq_table", "panda_sumcheck_plan",
 ]
 ALL_SYMBOLS = REFERENCE_SYMBOLS + RUST_ONLY_SYMBOLS + ADDITIVE_SYMBOLS
 
@@ -175,6 +179,10 @@ def load() -> C.CDLL:
         "panda_lookup_home_slot": [u, vp, u, C.POINTER(C.c_uint64)],
         "panda_poly_running_sum": [u, vp, vp, C.c_uint64, u, vp, PandaStream],
         "panda_poly_running_sum_plan": [C.c_uint64, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)],
+        "panda_sumcheck_round": [u, C.POINTER(SopExpression), u, u, u, vp, C.POINTER(vp), vp, PandaStream],
+        "panda_mle_fold": [u, C.POINTER(vp), C.POINTER(vp), u, u, u, vp, PandaStream],
+        "panda_mle_eq_table": [u, vp, u, vp, PandaStream],
+        "panda_sumcheck_plan": [u, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u)],
         "panda_msm_register_bases": [u, vp, u, PandaStream], "panda_msm_unregister_bases": [vp], "panda_msm_precompute_bases": [u, vp, u, u, PandaStream],
         "panda_msm_registered_info": [vp, C.POINTER(u), C.POINTER(u), C.POINTER(sz)], "panda_msm_set_chunk_entries": [u], "panda_msm_set_overlap": [u, u], "panda_msm_set_accumulate_variant": [u], "panda_msm_set_wide_merge": [u], "panda_msm_set_reduce_group": [u], "panda_msm_plain_window_plan": [u, u, C.POINTER(u), C.POINTER(u)], "panda_msm_verify_registered": [vp, PandaStream], "panda_msm_set_paranoid": [u], "panda_msm_set_phase_timing": [u], "panda_msm_setup_bls12_377": [], "panda_msm_execute_bls12_377": [MSMConfiguration], "panda_msm_execute_bls12_377_host": [MSMConfiguration],
         "panda_msm_set_window_bits": [u], "panda_msm_last_phase_ms": [C.POINTER(C.c_float)], "panda_ntt_last_device_ms": [C.POINTER(C.c_float)], "panda_ntt_pass_plan": [u, C.POINTER(C.c_uint), C.POINTER(C.c_uint)], "panda_ntt_set_streamed_tables": [u], "panda_ntt_execute_bn254_inverse": [NttconfigurationV1], "panda_ntt_execute_bls12_377_v1": [NttconfigurationV1], "panda_ntt_execute_bls12_377_inverse": [NttconfigurationV1],

@@ -779,3 +779,88 @@ def panda_poly_gpu_sum_of_products(gm: PandaGpuManager, columns, terms, field: i
         lib.panda_free(d)
         if d_out:
             lib.panda_free(d_out)
+
+
+def panda_mle_gpu_eq_table(gm: PandaGpuManager, point, field: int = 0) -> np.ndarray:
+    """Additive: the table eq(r, x) = prod_j (x_j r_j + (1 - x_j)(1 - r_j)) over x < 2^k for the point r = `point`, a (k, 8) uint32 array of
+    Montgomery-form elements (k may be 0), by ONE library call (panda_mle_eq_table).  Returns a (2^k, 8) uint32 array."""
+    pt = np.ascontiguousarray(point, np.uint32).reshape(-1, 8)
+    log_n = len(pt)
+    if log_n > 28:
+        raise PandaGpuError("SchedulingErr")
+    host = pt if log_n else np.zeros((1, 8), np.uint32)
+    lib = ffi.load()
+    d = C.c_void_p()
+    size = FIELD_ELEMENT_LEN << log_n
+    ffi.check(lib.panda_malloc(C.byref(d), size), "AsyncPoolMallocErr")
+    try:
+        ffi.check(lib.panda_mle_eq_table(field, _ptr(host), log_n, d, gm.exec_stream.raw), "SchedulingErr")
+        out = np.empty((1 << log_n, 8), np.uint32)
+        ffi.check(lib.panda_memcpy(_ptr(out), d, size), "CreateContextError")
+        return out
+    finally:
+        lib.panda_free(d)
+
+
+def panda_sumcheck_gpu_run(gm: PandaGpuManager, columns, terms, n_evals: int, challenges, field: int = 0, order: int = 0, fused: bool = False):
+    """Additive: the prover's side of a whole sumcheck over multilinear tables.  `columns` is a list of (2^k, 8) uint32 arrays of
+    Montgomery-form elements, k >= 1; `terms` a list of (coeff, [column, ...]) with coeff an 8-word element and an empty list for a
+    constant term; `challenges` a (k, 8) array, one per round, supplied by the caller (the transcript is the host's business); `order`
+    ffi.MLE_BIND_LOW or ffi.MLE_BIND_HIGH.  The tables are staged once and the rounds ping-pong between two buffer sets: with `fused` one
+    plain panda_sumcheck_round and k - 1 fused ones, otherwise a plain round and a panda_mle_fold per round; a last panda_mle_fold gives
+    the final values.  fused=False is the default: at 2^24 the fused rounds were faster on eq (a b - c) but not on the gate times eq
+    (DESIGN.md 5.7).  The host arrays are not
+    changed.  Returns (round_evals, final_values): a (k, n_evals, 8) array of g_j(0 .. n_evals - 1) and a (len(columns), 8) array of the
+    tables' values at the point of the challenges."""
+    cols = [np.ascontiguousarray(c, np.uint32) for c in columns]
+    ch = np.ascontiguousarray(challenges, np.uint32).reshape(-1, 8)
+    if not cols or not terms or cols[0].ndim != 2 or cols[0].shape[1] != 8 or any(c.shape != cols[0].shape for c in cols):
+        raise PandaGpuError("SchedulingErr")
+    n = cols[0].shape[0]
+    k = log_2(n)
+    if n < 2 or n != 1 << k or len(ch) != k or not 1 <= n_evals <= ffi.SUMCHECK_MAX_EVALS:
+        raise PandaGpuError("SchedulingErr")
+    coeffs = np.ascontiguousarray([np.asarray(c, np.uint32).reshape(8) for c, _ in terms], np.uint32)
+    degrees = (C.c_uint * len(terms))(*[len(fs) for _, fs in terms])
+    flat = [c for _, fs in terms for c in fs]
+    factors = (ffi.SopFactor * max(len(flat), 1))(*[ffi.SopFactor(c, 0) for c in flat])
+    lib = ffi.load()
+    m = len(cols)
+    size = n * FIELD_ELEMENT_LEN
+    d, _, _ = _stage_polys(gm, cols)
+    d_other = C.c_void_p()
+    try:
+        ffi.check(lib.panda_malloc(C.byref(d_other), m * (size // 2)), "AsyncPoolMallocErr")
+        stream = gm.exec_stream.raw
+        evals = np.zeros((k, n_evals, 8), np.uint32)
+        # the tables of round j are 2^(k - j) elements each; set 0 is the staged buffer, set 1 holds at most half-size tables
+        sets = ([d.value + c * size for c in range(m)], [d_other.value + c * (size // 2) for c in range(m)])
+
+        def pointers(which):
+            return (C.c_void_p * m)(*sets[which])
+
+        def round_call(j, src, challenge=None, dst=None):
+            expr = ffi.SopExpression(pointers(src), _ptr(coeffs), degrees, factors, None, m, len(terms), 0, ffi.SOP_SCALE_NONE)
+            log_n = k - j + (1 if dst is not None else 0)
+            ffi.check(lib.panda_sumcheck_round(field, C.byref(expr), log_n, order, n_evals, None if challenge is None else _ptr(challenge),
+                                               None if dst is None else pointers(dst), _ptr(evals[j]), stream), "SchedulingErr")
+
+        cur = 0
+        round_call(0, cur)
+        for j in range(1, k):
+            if fused:
+                round_call(j, cur, ch[j - 1], 1 - cur)
+                cur = 1 - cur
+            else:
+                ffi.check(lib.panda_mle_fold(field, pointers(cur), pointers(1 - cur), m, k - j + 1, order, _ptr(ch[j - 1]), stream), "SchedulingErr")
+                cur = 1 - cur
+                round_call(j, cur)
+        ffi.check(lib.panda_mle_fold(field, pointers(cur), pointers(1 - cur), m, 1, order, _ptr(ch[k - 1]), stream), "SchedulingErr")
+        final = np.empty((m, 8), np.uint32)
+        for c in range(m):
+            ffi.check(lib.panda_memcpy(_ptr(final[c]), C.c_void_p(sets[1 - cur][c]), FIELD_ELEMENT_LEN), "CreateContextError")
+        return evals, final
+    finally:
+        lib.panda_free(d)
+        if d_other:
+            lib.panda_free(d_other)
