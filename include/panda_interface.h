@@ -592,6 +592,53 @@ panda_error panda_mle_fold(unsigned field, const void *const *columns, void *con
                            const void *challenge /* HOST 32 B */, panda_stream stream);
 panda_error panda_mle_eq_table(unsigned field, const void *point /* HOST, log_n x 32 B */, unsigned log_n, void *d_out /* DEVICE 2^log_n x 32 B */, panda_stream stream);
 panda_error panda_sumcheck_plan(unsigned log_n, unsigned fused, unsigned n_evals, unsigned *tile_pairs, unsigned *carry_chunk, unsigned *launches);
+/* Sparse matrix-vector products over the scalar fields -- Az, Bz, Cz, the first step of every R1CS prover (Groth16, Marlin, Spartan), so
+ * that the witness is the only upload and the columns of every later call are born on the device.  The matrix is CSR; field: 0 BN254 Fr,
+ * 1 BLS12-377 Fr, 2 BLS12-381 Fr; elements are the 32-byte canonical Montgomery wire form of every other call, 16-byte aligned; a
+ * non-canonical input is outside the contract.
+ *
+ * The product.  For p < batch and r < n_rows:  out[p][r] = sum_{k in row r} values[k] z[p][col[k]].  Vector p of d_z is at byte
+ * p * n_cols * 32, vector p of d_out at byte p * n_rows * 32.  Outputs are canonical; an empty row gives the wire zero.  Field addition
+ * is exact, so the bytes are identical on every run whatever the order of the sums.  Synchronous on return.
+ *   Shapes: n_rows >= 1, n_cols >= 1, nnz >= 0 (nnz == 0 writes zeros; d_col and d_values may then be NULL), each <= 2^28; batch >= 1,
+ *     batch x n_rows <= 2^28 and batch x n_cols <= 2^28.
+ *   Aliasing: the matrix and d_z are read only and may overlap each other freely; d_out may overlap none of them, not even with exact
+ *     equality (the gather reads all of z).  Bytes behind d_out's batch x n_rows elements are never written.
+ *   The work is split by nonzeros, `tile` of them to a workgroup, so neither a row of millions of terms nor a run of millions of empty
+ *     rows is a loop in any thread.  d_out is zeroed, then two kernel launches (the tiles; the rows that cross a tile end, none for a
+ *     single tile); no kernel waits for another workgroup, no atomics on elements.  32 bytes per vector and tile go to the calling host
+ *     thread's arena scratch: a repeated call of the same shape allocates nothing, panda_ntt_tear_down releases it.  (A shape of more
+ *     than 2^31 - 1 vector-tiles, whose scratch alone is 64 GB, fails with the runtime's allocation error.)
+ *   Memory safety: whatever bytes d_row_ptr and d_col hold, no kernel reads or writes outside the stated extents of the six buffers: a
+ *     column index is compared with n_cols before it addresses z, a row index reaches d_out only below n_rows, a position reaches d_col
+ *     and d_values only below nnz.  For a structure the check below would reject the VALUES of out are unspecified; the accesses are not.
+ *   The transposed product is not offered (there is no atomic on a 256-bit residue): pass the CSR of the transpose.
+ *   panda_error_invalid_value, nothing launched, nothing written: field > 2, the shapes above, a NULL m / d_row_ptr / d_z / d_out, a NULL
+ *     d_col or d_values with nnz > 0, d_out overlapping any of the four inputs as address ranges, and buffers of this library's allocators
+ *     shorter than stated -- all checked before any runtime call.
+ *
+ * The check.  One pass over the structure that dereferences nothing through an index and reports the FIRST defect, the smallest class
+ * and then the smallest index (deterministic):  *defect = 0 none; 1 row_ptr[0] != 0; 2 row_ptr[r] > row_ptr[r + 1], *where = r;
+ * 3 row_ptr[n_rows] != nnz; 4 col[k] >= n_cols, *where = k; 5 values[k] >= the modulus, *where = k.  *where is UINT64_MAX without a defect
+ * and for the classes 1 and 3.  A defect is data: the call still returns panda_success.  Either out pointer may be NULL, not both.
+ * One launch, synchronous, 8 bytes of arena scratch; refuses the shapes and matrix pointers the product refuses.
+ *
+ * The plan (pure host arithmetic, no device call): *tile = the nonzeros one workgroup covers, *carry_chunk = the tiles the second launch
+ * adds per step and row, *scratch_bytes = the arena bytes, *launches = the kernel launches of the product, memsets not counted.  *tile
+ * and *carry_chunk depend on none of the arguments.  Any pointer may be NULL.  Invalid for exactly the shapes the product refuses. */
+typedef struct panda_csr_matrix
+{
+    const uint32_t *d_row_ptr; /* DEVICE, n_rows + 1 entries: row r holds the nonzeros row_ptr[r] .. row_ptr[r + 1] - 1 */
+    const uint32_t *d_col;     /* DEVICE, nnz entries, each < n_cols; any order inside a row, repeats allowed (they add) */
+    const void *d_values;      /* DEVICE, nnz x 32 B */
+    uint64_t n_rows, n_cols, nnz;
+} panda_csr_matrix;
+panda_error panda_sparse_matvec(unsigned field, const panda_csr_matrix *m, const void *d_z /* DEVICE, batch x n_cols x 32 B */,
+                                void *d_out /* DEVICE, batch x n_rows x 32 B */, unsigned batch, panda_stream stream);
+panda_error panda_sparse_check(unsigned field, const panda_csr_matrix *m, unsigned *defect /* HOST, may be NULL */,
+                               uint64_t *where /* HOST, may be NULL */, panda_stream stream);
+panda_error panda_sparse_plan(uint64_t n_rows, uint64_t n_cols, uint64_t nnz, unsigned batch, unsigned *tile, unsigned *carry_chunk,
+                              size_t *scratch_bytes, unsigned *launches);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

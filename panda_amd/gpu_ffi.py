@@ -89,6 +89,11 @@ class SopExpression(C.Structure):  # additive: include/panda_interface.h panda_s
                 ("scales", C.c_void_p), ("n_columns", C.c_uint), ("n_terms", C.c_uint), ("n_scales", C.c_uint), ("scale_mode", C.c_uint)]
 
 
+class CsrMatrix(C.Structure):  # additive: include/panda_interface.h panda_csr_matrix; every pointer is a DEVICE pointer
+    _fields_ = [("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_values", C.c_void_p), ("n_rows", C.c_uint64), ("n_cols", C.c_uint64),
+                ("nnz", C.c_uint64)]
+
+
 # every symbol include/panda_interface.h declares; tests assert the library exports each one
 REFERENCE_SYMBOLS = [
     "panda_get_device_number", "panda_get_device", "panda_set_device", "panda_stream_create", "panda_stream_wait_event",
@@ -126,6 +131,7 @@ ADDITIVE_SYMBOLS = [
     "panda_poly_sum_of_products", "panda_poly_sum_of_products_plan",
     "panda_lookup_multiplicities", "panda_lookup_plan", "panda_lookup_home_slot", "panda_poly_running_sum", "panda_poly_running_sum_plan",
     "panda_sumcheck_round", "panda_mle_fold", "panda_mle_eq_table", "panda_sumcheck_plan",
+    "panda_sparse_matvec", "panda_sparse_check", "panda_sparse_plan",
 ]
 ALL_SYMBOLS = REFERENCE_SYMBOLS + RUST_ONLY_SYMBOLS + ADDITIVE_SYMBOLS
 
@@ -183,6 +189,9 @@ def load() -> C.CDLL:
         "panda_mle_fold": [u, C.POINTER(vp), C.POINTER(vp), u, u, u, vp, PandaStream],
         "panda_mle_eq_table": [u, vp, u, vp, PandaStream],
         "panda_sumcheck_plan": [u, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u)],
+        "panda_sparse_matvec": [u, C.POINTER(CsrMatrix), vp, vp, u, PandaStream],
+        "panda_sparse_check": [u, C.POINTER(CsrMatrix), C.POINTER(u), C.POINTER(C.c_uint64), PandaStream],
+        "panda_sparse_plan": [C.c_uint64, C.c_uint64, C.c_uint64, u, C.POINTER(u), C.POINTER(u), C.POINTER(sz), C.POINTER(u)],
         "panda_msm_register_bases": [u, vp, u, PandaStream], "panda_msm_unregister_bases": [vp], "panda_msm_precompute_bases": [u, vp, u, u, PandaStream],
         "panda_msm_registered_info": [vp, C.POINTER(u), C.POINTER(u), C.POINTER(sz)], "panda_msm_set_chunk_entries": [u], "panda_msm_set_overlap": [u, u], "panda_msm_set_accumulate_variant": [u], "panda_msm_set_wide_merge": [u], "panda_msm_set_reduce_group": [u], "panda_msm_plain_window_plan": [u, u, C.POINTER(u), C.POINTER(u)], "panda_msm_verify_registered": [vp, PandaStream], "panda_msm_set_paranoid": [u], "panda_msm_set_phase_timing": [u], "panda_msm_setup_bls12_377": [], "panda_msm_execute_bls12_377": [MSMConfiguration], "panda_msm_execute_bls12_377_host": [MSMConfiguration],
         "panda_msm_set_window_bits": [u], "panda_msm_last_phase_ms": [C.POINTER(C.c_float)], "panda_ntt_last_device_ms": [C.POINTER(C.c_float)], "panda_ntt_pass_plan": [u, C.POINTER(C.c_uint), C.POINTER(C.c_uint)], "panda_ntt_set_streamed_tables": [u], "panda_ntt_execute_bn254_inverse": [NttconfigurationV1], "panda_ntt_execute_bls12_377_v1": [NttconfigurationV1], "panda_ntt_execute_bls12_377_inverse": [NttconfigurationV1],

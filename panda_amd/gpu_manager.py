@@ -864,3 +864,83 @@ def panda_sumcheck_gpu_run(gm: PandaGpuManager, columns, terms, n_evals: int, ch
         lib.panda_free(d)
         if d_other:
             lib.panda_free(d_other)
+
+
+class PandaSparseMatrix:
+    """Additive: a CSR matrix over a scalar field kept resident on the device across products -- the A, B or C of an R1CS, staged once
+    per circuit.  `row_ptr` holds n_rows + 1 and `col` nnz uint32 entries, `values` is an (nnz, 8) uint32 array of Montgomery-form elements
+    (field 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr).  The structure is checked once on the device (panda_sparse_check); a defect raises
+    PandaGpuError naming its class and index.  free() releases the device copy."""
+
+    DEFECTS = {1: "row_ptr[0] != 0", 2: "row_ptr decreases", 3: "row_ptr[n_rows] != nnz", 4: "column index >= n_cols", 5: "value >= modulus"}
+
+    def __init__(self, gm: PandaGpuManager, row_ptr, col, values, n_cols: int, field: int = 0):
+        rp = np.ascontiguousarray(row_ptr, np.uint32).reshape(-1)
+        cl = np.ascontiguousarray(col, np.uint32).reshape(-1)
+        vals = np.ascontiguousarray(values, np.uint32).reshape(-1, 8)
+        if len(rp) < 2 or len(vals) != len(cl) or n_cols < 1:
+            raise PandaGpuError("SchedulingErr")
+        self.gm, self.field = gm, field
+        self.n_rows, self.n_cols, self.nnz = len(rp) - 1, int(n_cols), len(cl)
+        lib = ffi.load()
+        self._bufs = []
+        try:
+            ptrs = [self._stage(lib, a) if a.size else None for a in (rp, cl, vals)]
+            gm.wait_h2d()
+            self.matrix = ffi.CsrMatrix(ptrs[0], ptrs[1], ptrs[2], self.n_rows, self.n_cols, self.nnz)
+            defect, where = C.c_uint(0), C.c_uint64(0)
+            ffi.check(lib.panda_sparse_check(field, C.byref(self.matrix), C.byref(defect), C.byref(where), gm.exec_stream.raw), "SchedulingErr")
+            if defect.value:
+                at = "" if where.value == 0xFFFFFFFFFFFFFFFF else f" at {where.value}"
+                raise PandaGpuError(f"SparseDefect{defect.value}: {self.DEFECTS.get(defect.value, '?')}{at}")
+        except Exception:
+            self.free()
+            raise
+
+    def _stage(self, lib, a: np.ndarray) -> int:
+        d = C.c_void_p()
+        ffi.check(lib.panda_malloc(C.byref(d), a.nbytes), "AsyncPoolMallocErr")
+        self._bufs.append(d)
+        ffi.check(lib.panda_memcpy_async(d, _ptr(a), a.nbytes, self.gm.h2d_stream.raw), "AsyncMemcopyErr")
+        return d.value
+
+    def matvec(self, z) -> np.ndarray:
+        """M z for z an (n_cols, 8) or (batch, n_cols, 8) uint32 array by ONE library call (panda_sparse_matvec); returns (n_rows, 8) or
+        (batch, n_rows, 8).  The host array is not changed."""
+        zs = np.ascontiguousarray(z, np.uint32)
+        if zs.ndim not in (2, 3) or zs.shape[-2:] != (self.n_cols, 8):
+            raise PandaGpuError("SchedulingErr")
+        batch = 1 if zs.ndim == 2 else zs.shape[0]
+        if batch == 0:
+            return np.empty((0, self.n_rows, 8), np.uint32)
+        lib = ffi.load()
+        d_z, _, _ = _stage_polys(self.gm, [zs.reshape(-1, 8)])
+        d_out = C.c_void_p()
+        try:
+            size = batch * self.n_rows * FIELD_ELEMENT_LEN
+            ffi.check(lib.panda_malloc(C.byref(d_out), size), "AsyncPoolMallocErr")
+            ffi.check(lib.panda_sparse_matvec(self.field, C.byref(self.matrix), d_z, d_out, batch, self.gm.exec_stream.raw), "SchedulingErr")
+            out = np.empty((self.n_rows, 8) if zs.ndim == 2 else (batch, self.n_rows, 8), np.uint32)
+            ffi.check(lib.panda_memcpy(_ptr(out), d_out, size), "CreateContextError")
+            return out
+        finally:
+            lib.panda_free(d_z)
+            if d_out:
+                lib.panda_free(d_out)
+
+    def free(self):
+        lib = ffi.load()
+        for d in self._bufs:
+            lib.panda_free(d)
+        self._bufs = []
+
+
+def panda_sparse_gpu_matvec(gm: PandaGpuManager, row_ptr, col, values, z, n_cols: int, field: int = 0) -> np.ndarray:
+    """Additive: the sparse product out[r] = sum_{k in row r} values[k] z[col[k]] of a CSR matrix and a vector (or a batch of vectors) over
+    a scalar field: stages the matrix, checks its structure on the device (a defect raises PandaGpuError), runs panda_sparse_matvec and
+    returns the product.  A caller with one circuit and many witnesses keeps a PandaSparseMatrix instead."""
+    m = PandaSparseMatrix(gm, row_ptr, col, values, n_cols, field)
+    try:
+        return m.matvec(z)
+    finally:
+        m.free()
