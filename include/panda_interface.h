@@ -804,6 +804,14 @@ panda_error panda_debug_curve_op(unsigned curve, unsigned op, void *d_r, const v
  * outside the table.  Device pointers. */
 panda_error panda_debug_fe_internal(unsigned field_id, unsigned op, void *d_r, const void *d_a, const void *d_b, const void *d_c, const void *d_d, size_t n,
                                     panda_stream stream);
+/* The XYZZ group law of csrc/curve29.h on INTERNAL-form points, with no wire conversion on the way in, so that a point can sit anywhere
+ * inside the stored-point contract (X below (8+M) p loose, Y below YB p, ZZ and ZZZ below 2p tight).  A stored point is the 4 W u32
+ * limbs the MSM kernels store (X, Y, ZZ, ZZZ; W = N limbs, 2 N for G2), an affine base 2 W limbs.  curve as panda_debug_curve_op;
+ * op: the table of csrc/curve29_debug_ops.h (0 = madd_core, 1 = madd, 2 = madd_neg, 3 = madd_neg_raw, 4 = madd_trace, 5 = dbl_affine,
+ * 6 = dbl, 7 = add, 8 / 9 = the four-lane add / dbl, 10..12 = to Jacobian wire, homogeneous wire, internal affine), which also gives
+ * the width of r per element; d_a or d_b may be NULL where the op takes none.  panda_error_invalid_value, with nothing launched, for a
+ * bad curve or a (curve, op) pair outside the table.  Device pointers. */
+panda_error panda_debug_xyzz_internal(unsigned curve, unsigned op, void *d_r, const void *d_a, const void *d_b, size_t n, panda_stream stream);
 
 const char *panda_version(void);
 

@@ -5,6 +5,7 @@
 // time with the oracle (reference counterparts: field.cuh:139-619, projective.cuh:163-314).
 // panda_gen_scalars / panda_gen_bases build the SURVEY section 8d inputs directly in HBM: 2^26 bases
 // (4 GiB) cannot sensibly be generated on the host and shipped over PCIe.
+#include "curve29_debug_ops.h"
 #include "curve29_quad.h"
 #include "fe29_debug_ops.h"
 #include "panda_internal.h"
@@ -13,29 +14,9 @@ using namespace panda29;
 
 namespace {
 
-// Out-of-line copies of the heavy group operations for the 14-limb fields: these diagnostic kernels are not timed, and
+// The out-of-line copies of the heavy group operations (madd_outlined, add_outlined, dbl_outlined, to_affine_outlined and the two quad
+// ones) live in curve29_debug_ops.h, one per field, shared by every kernel of this file: the diagnostic kernels are not timed, and
 // inlining every operation for every curve made this file the longest compile of the library.
-template <class F>
-__device__ __noinline__ void to_affine_outlined(Fe<F> &x, Fe<F> &y, const Xyzz<F> &p)
-{
-    xyzz_to_affine_internal(x, y, p);
-}
-template <class F>
-__device__ __noinline__ void madd_outlined(Xyzz<F> &acc, const Fe<F> &x, const Fe<F> &y, bool inf)
-{
-    xyzz_madd(acc, x, y, inf);
-}
-template <class F>
-__device__ __noinline__ void add_outlined(Xyzz<F> &acc, const Xyzz<F> &q)
-{
-    xyzz_add(acc, q);
-}
-template <class F>
-__device__ __noinline__ void dbl_outlined(Xyzz<F> &r, const Xyzz<F> &p)
-{
-    xyzz_dbl(r, p);
-}
-
 
 template <class F>
 __global__ void __launch_bounds__(256) k_field_op(unsigned op, u32 *__restrict__ r, const u32 *__restrict__ a, const u32 *__restrict__ b, size_t n)
@@ -105,17 +86,6 @@ __global__ void __launch_bounds__(128) k_curve_op(unsigned op, u32 *__restrict__
 
 // ops 3 / 4: the four-lane addition / doubling of curve29_quad.h (what the MSM's fix-up and bucket-reduction trees run), one QUAD per element
 template <class F>
-__device__ __noinline__ void add_quad_outlined(Xyzz<F> &acc, const Xyzz<F> &q, unsigned role)
-{
-    xyzz_add_quad(acc, q, role);
-}
-template <class F>
-__device__ __noinline__ void dbl_quad_outlined(Xyzz<F> &r, const Xyzz<F> &p, unsigned role)
-{
-    xyzz_dbl_quad(r, p, role);
-}
-
-template <class F>
 __global__ void __launch_bounds__(128) k_curve_op_quad(unsigned op, u32 *__restrict__ r, const u32 *__restrict__ a, const u32 *__restrict__ b, size_t n)
 {
     constexpr int L = F::L;
@@ -157,6 +127,30 @@ hipError_t launch_fe_internal(unsigned op, u32 *r, const u32 *a, const u32 *b, c
 {
     if (!fe29_debug_supported<F>(op)) return hipErrorInvalidValue;
     if (n) hipLaunchKernelGGL(k_fe_internal<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, r, a, b, c, d, n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
+}
+
+// the op table of curve29_debug_ops.h on internal-form points (panda_debug_xyzz_internal); the host twin is
+// tests/host_check/curve29_internal_host.cpp.  PER = 1 thread per element, or 4 for the two quad ops: whole quads leave together.
+template <class F, int PER>
+__global__ void __launch_bounds__(128) k_xyzz_internal(unsigned op, u32 *r, const u32 *a, const u32 *b, size_t n)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t i = t / PER;
+    if (i >= n) return;
+    xyzz_debug_op<F, PER == 4 ? XYZZ_DBG_QUAD : XYZZ_DBG_SEQUENTIAL>(op, r, a, b, i, PER == 4 ? (threadIdx.x & 3u) : 0u); // each kernel compiles its part of the table only
+}
+
+template <class F>
+hipError_t launch_xyzz_internal(unsigned op, u32 *r, const u32 *a, const u32 *b, size_t n, hipStream_t s)
+{
+    if (!xyzz_debug_supported<F>(op)) return hipErrorInvalidValue;
+    if (n && xyzz_debug_is_quad(op))
+        hipLaunchKernelGGL((k_xyzz_internal<F, 4>), dim3((unsigned)((4 * n + 127) / 128)), dim3(128), 0, s, op, r, a, b, n);
+    else if (n)
+        hipLaunchKernelGGL((k_xyzz_internal<F, 1>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, op, r, a, b, n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return e;
@@ -460,6 +454,24 @@ panda_error panda_debug_fe_internal(unsigned field_id, unsigned op, void *d_r, c
     case 7: e = launch_fe_internal<Ext2<Bls381Fq>>(op, r, a, b, c, d, n, s); break;
     case 8: e = launch_fe_internal<Ext2<Bls377Fq>>(op, r, a, b, c, d, n, s); break;
     default: return panda_error_invalid_value;
+    }
+    return e == hipErrorInvalidValue ? panda_error_invalid_value : static_cast<panda_error>(e);
+}
+
+panda_error panda_debug_xyzz_internal(unsigned curve, unsigned op, void *d_r, const void *d_a, const void *d_b, size_t n, panda_stream stream)
+{
+    if (!panda::msm_curve_valid(curve)) return panda_error_invalid_value;
+    hipStream_t s = static_cast<hipStream_t>(stream.handle);
+    u32 *r = (u32 *)d_r;
+    const u32 *a = (const u32 *)d_a, *b = (const u32 *)d_b;
+    hipError_t e;
+    switch (curve) {
+    case 0: e = launch_xyzz_internal<Bn254Fq>(op, r, a, b, n, s); break;
+    case 1: e = launch_xyzz_internal<Bls377Fq>(op, r, a, b, n, s); break;
+    case 2: e = launch_xyzz_internal<Bls381Fq>(op, r, a, b, n, s); break;
+    case 3: e = launch_xyzz_internal<Ext2<Bn254Fq>>(op, r, a, b, n, s); break;
+    case 4: e = launch_xyzz_internal<Ext2<Bls381Fq>>(op, r, a, b, n, s); break;
+    default: e = launch_xyzz_internal<Ext2<Bls377Fq>>(op, r, a, b, n, s); break;
     }
     return e == hipErrorInvalidValue ? panda_error_invalid_value : static_cast<panda_error>(e);
 }
