@@ -14,8 +14,9 @@
  * (binding.rs:14,16,54-56).  Part 3 is additive (no reference counterpart): BLS12-377 / BLS12-381 / BN254 G2 / BLS12-381 G2 / BLS12-377 G2,
  * cached-base registration and tables, the in-call upload pipeline, inverse / coset / bit-reversed NTTs, batches, the low-degree
  * extension, polynomial evaluation and division by X - z, batch inversion and grand products over the scalar fields, fused sums of
- * products, logUp lookup support (multiplicities and running sums), sumcheck rounds over multilinear tables, multi-GPU halves and
- * synthetic-input / diagnostics entry points.
+ * products, logUp lookup support (multiplicities and running sums), sumcheck rounds over multilinear tables, sparse matrix-vector
+ * products, the EC-NTT over G1 with batch affine normalisation of device points, multi-GPU halves and synthetic-input / diagnostics
+ * entry points.
  *
  * Conventions (unchanged from the reference):
  *   - return value: the HIP runtime's error code cast to unsigned; 0 = success
@@ -639,6 +640,57 @@ panda_error panda_sparse_check(unsigned field, const panda_csr_matrix *m, unsign
                                uint64_t *where /* HOST, may be NULL */, panda_stream stream);
 panda_error panda_sparse_plan(uint64_t n_rows, uint64_t n_cols, uint64_t nnz, unsigned batch, unsigned *tile, unsigned *carry_chunk,
                               size_t *scratch_bytes, unsigned *launches);
+/* The discrete Fourier transform over G1 points, and the batch conversion of result triples to affine points.  Both turn a vector of
+ * points into a vector of points on the device: the first makes the Lagrange-basis SRS [L_i(tau)]G out of the monomial one (the inverse
+ * transform: Q_i = n^-1 sum_j omega^(-ij) P_j) and is the core of amortised KZG openings, the second makes what panda_msm_execute_batch
+ * returns fit for a transcript or for panda_msm_register_bases.  curve: 0 BN254, 1 BLS12-377, 2 BLS12-381, G1 only; the G2 ids (3, 4, 6)
+ * are refused.  The reference has neither call.
+ *
+ * panda_ec_ntt.  out[k] = sum_j omega^(jk) P_j for k, j < n = 2^log_n, natural order in and out; PANDA_EC_NTT_INVERSE uses omega^-1 and
+ * multiplies by n^-1, as panda_ntt_execute_*_inverse do.  `omega` is the FORWARD root for both directions: a HOST pointer to one
+ * Montgomery-form scalar of 32 B, the convention of panda_ntt_configuration_v1.d_omega.  0 <= log_n <= PANDA_EC_NTT_MAX_LOG_N; log_n == 0
+ * copies the point (omega is not read then, but must not be NULL).  Synchronous on return.
+ *   Formats: d_in and d_out are n affine base points in the wire form the MSM takes, x || y, 64 B on BN254 and 96 B on the BLS curves,
+ *     16-byte aligned.  x == 0 is the identity on input; on output the identity is all-zero bytes.  Output coordinates are canonical, so
+ *     the bytes are the same on every run and the output can go straight to panda_msm_register_bases / panda_msm_precompute_bases.
+ *   Aliasing: d_out == d_in exactly is in place and legal, any other overlap is refused.  Bytes behind d_out's n points are never
+ *     written; d_in is unchanged by an out-of-place call.
+ *   Scratch: the intermediate points (XYZZ, 144 B on BN254, 224 B on the BLS curves) and the table of the n / 2 canonical twiddles (32 B
+ *     each, built on the device by every call) live in the calling host thread's arena: a repeated call of the same shape allocates
+ *     nothing, panda_ntt_tear_down releases it.
+ *   Invalid inputs: points off the curve or outside the prime-order subgroup, and non-canonical coordinates, are outside the contract:
+ *     the VALUES are then unspecified, the memory accesses are not -- no index is ever derived from point data.
+ *   The method is radix-2 over the points, one launch per stage; a multiplication by a twiddle is a double-and-add over its 256 bits.
+ *     In the stages where at least 64 butterflies share a twiddle a wave runs 64 butterflies of one twiddle, so its bits are
+ *     wave-uniform and a zero bit costs a doubling only; the other stages pay a doubling and an addition per bit.  P + P, P + (-P) and
+ *     the identity take the exact paths of the group law.  No kernel waits for another workgroup; there are no atomics.
+ *   panda_error_invalid_value, nothing launched, nothing written: curve > 2, log_n > PANDA_EC_NTT_MAX_LOG_N, direction > 1, a NULL d_in /
+ *     d_out / omega, for log_n >= 1 an omega >= the modulus or with omega^(2^(log_n - 1)) != -1 (not a primitive 2^log_n-th root), the
+ *     overlaps above, and buffers of this library's allocators shorter than stated -- all checked before any runtime call.
+ *   The plan (pure host arithmetic): *launches = the kernel launches of the call, *scratch_bytes = its arena bytes, *uniform_stages = the
+ *     stages in which every wave's butterflies share one twiddle (the first, which multiplies by nothing, included).  Any pointer may be
+ *     NULL.  Invalid for curve > 2, log_n > the cap, direction > 1.
+ *
+ * panda_points_to_affine.  d_in holds n points as X || Y || Z triples in the MSM result form (96 B on BN254, 144 B on the BLS curves;
+ * JACOBIAN x = X / Z^2, y = Y / Z^3 or PROJECTIVE x = X / Z, y = Y / Z by in_type; identity <=> Z == 0), d_out receives n affine wire
+ * points, canonical, the identity as all-zero bytes.  1 <= n <= 2^28.  One launch, no scratch, synchronous on return: a thread takes
+ * `chunk` consecutive points, forms the prefix products of their Z (skipping identities; the products are parked in the output slots),
+ * inverts once and walks back.  The last chunk is short; a chunk of identities alone inverts nothing.
+ *   Aliasing: any overlap of the two buffers is refused.  d_in is unchanged; bytes behind d_out's n points are never written.
+ *   panda_error_invalid_value, nothing launched, nothing written: curve > 2, an in_type that is neither, n == 0 or n > 2^28, a NULL
+ *     pointer, overlapping buffers, buffers of this library's allocators shorter than stated -- all checked before any runtime call.
+ *   The plan: *chunk = the points per inversion (it depends on nothing), *launches = 1.  Either pointer may be NULL.  Invalid for n == 0
+ *     and n > 2^28. */
+#define PANDA_EC_NTT_FORWARD 0u
+#define PANDA_EC_NTT_INVERSE 1u   /* omega^-1 and the n^-1 scaling, as panda_ntt_execute_*_inverse */
+#define PANDA_EC_NTT_MAX_LOG_N 26 /* the MSM's own cap: a larger base set has no consumer */
+panda_error panda_ec_ntt(unsigned curve, const void *d_in, void *d_out, unsigned log_n, unsigned direction,
+                         const void *omega /* HOST, 32 B */, panda_stream stream);
+panda_error panda_ec_ntt_plan(unsigned curve, unsigned log_n, unsigned direction, unsigned *launches, size_t *scratch_bytes,
+                              unsigned *uniform_stages);
+panda_error panda_points_to_affine(unsigned curve, const void *d_in, panda_msm_result_coordinate_type in_type, void *d_out, uint64_t n,
+                                   panda_stream stream);
+panda_error panda_points_to_affine_plan(uint64_t n, unsigned *chunk, unsigned *launches);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

@@ -944,3 +944,63 @@ def panda_sparse_gpu_matvec(gm: PandaGpuManager, row_ptr, col, values, z, n_cols
         return m.matvec(z)
     finally:
         m.free()
+
+
+def _stage_bytes(lib, a: np.ndarray) -> C.c_void_p:
+    d = C.c_void_p()
+    ffi.check(lib.panda_malloc(C.byref(d), a.nbytes), "CreateContextError")
+    try:
+        ffi.check(lib.panda_memcpy(d, _ptr(a), a.nbytes), "CreateContextError")
+    except PandaGpuError:
+        lib.panda_free(d)
+        raise
+    return d
+
+
+def panda_ec_ntt_gpu(gm: PandaGpuManager, points, omega, curve: int = BN254, inverse: bool = False) -> np.ndarray:
+    """Additive: the discrete Fourier transform of n = 2^k affine G1 points (the MSM's base wire form, x || y, identity <=> x == 0) over
+    the group, out[k] = sum_j omega^(jk) P_j, natural order; `omega` is the FORWARD root of order n (one Montgomery-form scalar, 32 B)
+    for both directions, and inverse=True uses omega^-1 and multiplies by 1 / n -- the inverse transform of a monomial SRS is the
+    Lagrange-basis SRS.  One library call (panda_ec_ntt, in place on the device copy); the host array is not changed.  Returns
+    (n, point bytes) uint8: canonical affine points, the identity as all-zero bytes, ready for add_cached_bases.  curve is a G1 id."""
+    lib = ffi.load()
+    pb = _POINT_BYTES[curve]
+    h = _as_bytes(points)
+    n = h.size // pb
+    if n == 0 or n & (n - 1) or n * pb != h.size:
+        raise PandaGpuError("InvalidLengthErr")
+    om = _as_bytes(omega)
+    if om.size != FIELD_ELEMENT_LEN:
+        raise PandaGpuError("InvalidLengthErr")
+    d = _stage_bytes(lib, h)
+    try:
+        ffi.check(lib.panda_ec_ntt(curve, d, d, log_2(n), ffi.EC_NTT_INVERSE if inverse else ffi.EC_NTT_FORWARD, _ptr(om), gm.exec_stream.raw), "SchedulingErr")
+        out = np.empty(h.size, np.uint8)
+        ffi.check(lib.panda_memcpy(_ptr(out), d, h.size), "CreateContextError")
+    finally:
+        lib.panda_free(d)
+    return out.reshape(n, pb)
+
+
+def panda_points_gpu_to_affine(gm: PandaGpuManager, points, curve: int = BN254, projective: bool = False) -> np.ndarray:
+    """Additive: n result triples X || Y || Z (what the MSM calls return: Jacobian, or homogeneous with projective=True; identity <=>
+    Z == 0) -> n affine wire points (canonical, the identity as all-zero bytes) by ONE library call (panda_points_to_affine: one field
+    inversion per chunk of points).  Returns (n, point bytes) uint8.  curve is a G1 id."""
+    lib = ffi.load()
+    rb, pb = _RESULT_BYTES[curve], _POINT_BYTES[curve]
+    h = _as_bytes(points)
+    n = h.size // rb
+    if n == 0 or n * rb != h.size:
+        raise PandaGpuError("InvalidLengthErr")
+    d_in = _stage_bytes(lib, h)
+    d_out = C.c_void_p()
+    try:
+        ffi.check(lib.panda_malloc(C.byref(d_out), n * pb), "CreateContextError")
+        ffi.check(lib.panda_points_to_affine(curve, d_in, PROJECTIVE if projective else JACOBIAN, d_out, n, gm.exec_stream.raw), "SchedulingErr")
+        out = np.empty(n * pb, np.uint8)
+        ffi.check(lib.panda_memcpy(_ptr(out), d_out, n * pb), "CreateContextError")
+    finally:
+        lib.panda_free(d_in)
+        if d_out:
+            lib.panda_free(d_out)
+    return out.reshape(n, pb)
