@@ -691,6 +691,67 @@ panda_error panda_ec_ntt_plan(unsigned curve, unsigned log_n, unsigned direction
 panda_error panda_points_to_affine(unsigned curve, const void *d_in, panda_msm_result_coordinate_type in_type, void *d_out, uint64_t n,
                                    panda_stream stream);
 panda_error panda_points_to_affine_plan(uint64_t n, unsigned *chunk, unsigned *launches);
+/* Element-wise scalar multiplication of a vector of G1 points, and with it the KZG proofs of one polynomial at ALL points of its domain
+ * (Feist-Khovratovich).  curve: 0 BN254, 1 BLS12-377, 2 BLS12-381, G1 only; the G2 ids (3, 4, 6) are refused.  The reference has neither.
+ *
+ * panda_points_scalar_mul.  out[i] = A_i + k_i P_i for i < n, 1 <= n <= 2^28; the A_i term is omitted when d_addend is NULL.
+ *   mode PANDA_POINTS_MUL_EACH:   k_i = d_scalars[i] (DEVICE, n x 32 B); h_scalars must be NULL.  The FK20 product, folds of commitments.
+ *   mode PANDA_POINTS_MUL_ONE:    k_i = the one scalar at h_scalars (HOST, 32 B); d_scalars must be NULL.  The IPA fold, blinding.
+ *   mode PANDA_POINTS_MUL_POWERS: k_i = c s^i with (c, s) at h_scalars (HOST, 64 B); d_scalars must be NULL.  A powers-of-tau update,
+ *     the coset shift of a Lagrange SRS.
+ *   Formats: d_points, d_addend and d_out are n affine points in the wire form the MSM takes (x || y, 64 B on BN254, 96 B on the BLS
+ *     curves, 16-byte aligned); x == 0 is the identity on input, on output the identity is all-zero bytes and coordinates are canonical.
+ *     Scalars are 32-byte Montgomery-form residues of the curve's Fr, as in every other call.  Synchronous on return.
+ *   Aliasing: d_out is written by the second launch only, after every input has been read, so d_out == d_points or d_out == d_addend
+ *     exactly is legal; any other overlap among d_points, d_addend and d_out is refused.  Inputs of an out-of-place call are unchanged;
+ *     bytes behind d_out's n points are never written.
+ *   Method: two launches.  The first forms k_i P_i by left-to-right double-and-add, adds A_i and writes an XYZZ point (144 B on BN254,
+ *     224 B on the BLS curves) to the calling host thread's arena (a repeated call of the same shape allocates nothing,
+ *     panda_ntt_tear_down releases it); the second is the batch normalisation of panda_ec_ntt.  The loop runs over the longest scalar
+ *     of a wave of 64 points, not over 256 bits: a vector of 128-bit challenges costs 128 steps.  In ONE mode every branch on the
+ *     scalar is wave-uniform and a zero bit costs a doubling only; in the other modes a wave pays the doubling and the addition for
+ *     every step.  k_i = 0, P_i the identity, A_i = -k_i P_i and A_i = k_i P_i take the exact paths of the group law.
+ *   Invalid inputs: points off the curve, non-canonical coordinates and a DEVICE scalar at or above the modulus are outside the
+ *     contract: the values are then unspecified, the memory accesses are not -- no index is derived from point or scalar data.
+ *   panda_error_invalid_value, nothing launched, nothing written: curve > 2, mode > 2, n == 0 or n > 2^28, a NULL d_points / d_out, the
+ *     scalar pointer of the chosen mode NULL or the pointer of the other kind non-NULL, a host scalar >= the modulus, the overlaps above,
+ *     and buffers of this library's allocators shorter than stated -- all checked before any runtime call.
+ *   The plan (pure host arithmetic): *launches = 2, *scratch_bytes = n x the XYZZ point rounded up to 256, plus 256.  Either pointer may
+ *     be NULL.  Invalid for the shapes the call refuses.
+ *
+ * panda_kzg_open_all.  d_proofs[k] = the commitment to (f(X) - f(w^k)) / (X - w^k) under the SRS s_i = [tau^i]G, for all k < n = 2^log_n,
+ * 1 <= log_n <= PANDA_KZG_OPEN_ALL_MAX_LOG_N, w = omega2^2.  `omega2` is a HOST pointer to one Montgomery-form scalar (32 B): a primitive
+ * 2n-th root of unity, in the convention of panda_ec_ntt's omega and checked the same way.  With h_m = sum_{i <= n-2-m} f_(m+1+i) s_i
+ * (h_(n-1) the identity) the proofs are the EC-DFT of h, and h_m is entry n - 1 + m of the linear convolution of f with the reversed SRS
+ * s'_j = s_(n-2-j): 2n - 2 entries, so a cyclic convolution of length 2n does not wrap.
+ *   panda_kzg_open_all_setup: d_table (2n points) = the forward EC-NTT of size 2n of (s'_0 .. s'_(n-2), n + 1 identities): one copy kernel
+ *     and panda_ec_ntt in place.  Once per SRS and size.  d_srs (n points) is not modified; d_table must not overlap it.
+ *   panda_kzg_open_all: d_coeffs (n scalars) padded with n zeros into d_work; panda_ntt_execute_batch forward at size 2n (one member);
+ *     panda_points_scalar_mul EACH against d_table; panda_ec_ntt inverse at size 2n; entries n - 1 .. 2n - 3 and one identity into
+ *     d_proofs; panda_ec_ntt forward at size n with omega2^2 in place in d_proofs.  About 2n log 2n + n log n scalar multiplications of
+ *     points in place of n MSMs of size n.  Synchronous on return.  d_coeffs and d_table are unchanged; bytes behind the n proofs are
+ *     never written.  Proofs are affine wire points, canonical, the identity as all-zero bytes.
+ *   Workspace: d_work holds the temporaries (the parts take the calling thread's arena themselves): *work_bytes of the plan = 2n x 32 B +
+ *     2n x point bytes, rounded up to 256.  Its contents after a call are unspecified.
+ *   panda_error_invalid_value, nothing launched, nothing written: as for the parts, and: log_n == 0 or > the cap, a NULL pointer, an
+ *     omega2 >= the modulus or with omega2^n != -1, work_bytes below the plan's, any overlap among d_coeffs, d_table, d_work and d_proofs
+ *     (setup: between d_srs and d_table), buffers of this library's allocators shorter than stated -- all before any runtime call.
+ *   The plan: *launches = 1 (pad) + the passes of the scalar transform (panda_ntt_batch_plan at log_n + 1) + panda_points_scalar_mul_plan's
+ *     + panda_ec_ntt_plan's at (log_n + 1, inverse) + 1 (the middle copy) + panda_ec_ntt_plan's at (log_n, forward).  Either pointer may
+ *     be NULL.  Invalid for curve > 2, log_n == 0 and log_n > the cap. */
+#define PANDA_POINTS_MUL_EACH 0u
+#define PANDA_POINTS_MUL_ONE 1u
+#define PANDA_POINTS_MUL_POWERS 2u
+#define PANDA_KZG_OPEN_ALL_MAX_LOG_N 25 /* 2n within PANDA_EC_NTT_MAX_LOG_N */
+panda_error panda_points_scalar_mul(unsigned curve, unsigned mode, const void *d_points, const void *d_scalars /* DEVICE, mode EACH */,
+                                    const void *h_scalars /* HOST, modes ONE (32 B) and POWERS (64 B: c, s) */,
+                                    const void *d_addend /* DEVICE, may be NULL */, void *d_out, uint64_t n, panda_stream stream);
+panda_error panda_points_scalar_mul_plan(unsigned curve, unsigned mode, uint64_t n, unsigned *launches, size_t *scratch_bytes);
+panda_error panda_kzg_open_all_setup(unsigned curve, const void *d_srs /* n points [tau^i]G */, unsigned log_n, const void *omega2 /* HOST, 32 B */,
+                                     void *d_table /* 2n points */, panda_stream stream);
+panda_error panda_kzg_open_all(unsigned curve, const void *d_coeffs /* n scalars */, const void *d_table, unsigned log_n, const void *omega2,
+                               void *d_work, size_t work_bytes, void *d_proofs /* n points */, panda_stream stream);
+panda_error panda_kzg_open_all_plan(unsigned curve, unsigned log_n, size_t *work_bytes, unsigned *launches);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

@@ -75,6 +75,9 @@ SUMCHECK_MAX_EVALS = 8  # PANDA_SUMCHECK_MAX_EVALS
 # `direction` of panda_ec_ntt (PANDA_EC_NTT_FORWARD, PANDA_EC_NTT_INVERSE) and its largest log2 of the size
 EC_NTT_FORWARD, EC_NTT_INVERSE = 0, 1
 EC_NTT_MAX_LOG_N = 26  # PANDA_EC_NTT_MAX_LOG_N
+# `mode` of panda_points_scalar_mul (PANDA_POINTS_MUL_*) and the largest log2 of a panda_kzg_open_all domain
+POINTS_MUL_EACH, POINTS_MUL_ONE, POINTS_MUL_POWERS = 0, 1, 2
+KZG_OPEN_ALL_MAX_LOG_N = 25  # PANDA_KZG_OPEN_ALL_MAX_LOG_N
 CLOCK_WORDS, CLOCK_STAMP_BYTES = 12, 32768  # PANDA_CLOCK_WORDS, PANDA_CLOCK_STAMP_BYTES
 
 
@@ -136,6 +139,7 @@ ADDITIVE_SYMBOLS = [
     "panda_sumcheck_round", "panda_mle_fold", "panda_mle_eq_table", "panda_sumcheck_plan",
     "panda_sparse_matvec", "panda_sparse_check", "panda_sparse_plan",
     "panda_ec_ntt", "panda_ec_ntt_plan", "panda_points_to_affine", "panda_points_to_affine_plan",
+    "panda_points_scalar_mul", "panda_points_scalar_mul_plan", "panda_kzg_open_all_setup", "panda_kzg_open_all", "panda_kzg_open_all_plan",
 ]
 ALL_SYMBOLS = REFERENCE_SYMBOLS + RUST_ONLY_SYMBOLS + ADDITIVE_SYMBOLS
 
@@ -198,6 +202,9 @@ def load() -> C.CDLL:
         "panda_sparse_plan": [C.c_uint64, C.c_uint64, C.c_uint64, u, C.POINTER(u), C.POINTER(u), C.POINTER(sz), C.POINTER(u)],
         "panda_ec_ntt": [u, vp, vp, u, u, vp, PandaStream], "panda_ec_ntt_plan": [u, u, u, C.POINTER(u), C.POINTER(sz), C.POINTER(u)],
         "panda_points_to_affine": [u, vp, C.c_int, vp, C.c_uint64, PandaStream], "panda_points_to_affine_plan": [C.c_uint64, C.POINTER(u), C.POINTER(u)],
+        "panda_points_scalar_mul": [u, u, vp, vp, vp, vp, vp, C.c_uint64, PandaStream], "panda_points_scalar_mul_plan": [u, u, C.c_uint64, C.POINTER(u), C.POINTER(sz)],
+        "panda_kzg_open_all_setup": [u, vp, u, vp, vp, PandaStream], "panda_kzg_open_all": [u, vp, vp, u, vp, vp, sz, vp, PandaStream],
+        "panda_kzg_open_all_plan": [u, u, C.POINTER(sz), C.POINTER(u)],
         "panda_msm_register_bases": [u, vp, u, PandaStream], "panda_msm_unregister_bases": [vp], "panda_msm_precompute_bases": [u, vp, u, u, PandaStream],
         "panda_msm_registered_info": [vp, C.POINTER(u), C.POINTER(u), C.POINTER(sz)], "panda_msm_set_chunk_entries": [u], "panda_msm_set_overlap": [u, u], "panda_msm_set_accumulate_variant": [u], "panda_msm_set_wide_merge": [u], "panda_msm_set_reduce_group": [u], "panda_msm_plain_window_plan": [u, u, C.POINTER(u), C.POINTER(u)], "panda_msm_verify_registered": [vp, PandaStream], "panda_msm_set_paranoid": [u], "panda_msm_set_phase_timing": [u], "panda_msm_setup_bls12_377": [], "panda_msm_execute_bls12_377": [MSMConfiguration], "panda_msm_execute_bls12_377_host": [MSMConfiguration],
         "panda_msm_set_window_bits": [u], "panda_msm_last_phase_ms": [C.POINTER(C.c_float)], "panda_ntt_last_device_ms": [C.POINTER(C.c_float)], "panda_ntt_pass_plan": [u, C.POINTER(C.c_uint), C.POINTER(C.c_uint)], "panda_ntt_set_streamed_tables": [u], "panda_ntt_execute_bn254_inverse": [NttconfigurationV1], "panda_ntt_execute_bls12_377_v1": [NttconfigurationV1], "panda_ntt_execute_bls12_377_inverse": [NttconfigurationV1],

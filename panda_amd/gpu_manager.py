@@ -1004,3 +1004,98 @@ def panda_points_gpu_to_affine(gm: PandaGpuManager, points, curve: int = BN254, 
         if d_out:
             lib.panda_free(d_out)
     return out.reshape(n, pb)
+
+
+def panda_points_gpu_scalar_mul(gm: PandaGpuManager, points, scalars, curve: int = BN254, mode: int = ffi.POINTS_MUL_EACH, addend=None) -> np.ndarray:
+    """Additive: out[i] = addend[i] + k_i points[i] over n affine G1 points (the MSM's base wire form, identity <=> x == 0) by ONE library
+    call (panda_points_scalar_mul).  `scalars` are Montgomery-form Fr elements of 32 B: n of them with mode POINTS_MUL_EACH (k_i =
+    scalars[i]), one with POINTS_MUL_ONE (the same k for every point), two with POINTS_MUL_POWERS ((c, s): k_i = c s^i).  The host arrays
+    are not changed.  Returns (n, point bytes) uint8: canonical affine points, the identity as all-zero bytes.  curve is a G1 id."""
+    lib = ffi.load()
+    pb = _POINT_BYTES[curve]
+    h = _as_bytes(points)
+    n = h.size // pb
+    sc = _as_bytes(scalars)
+    want = {ffi.POINTS_MUL_EACH: n, ffi.POINTS_MUL_ONE: 1, ffi.POINTS_MUL_POWERS: 2}.get(mode)
+    if n == 0 or n * pb != h.size or want is None or sc.size != want * FIELD_ELEMENT_LEN:
+        raise PandaGpuError("InvalidLengthErr")
+    add = None if addend is None else _as_bytes(addend)
+    if add is not None and add.size != h.size:
+        raise PandaGpuError("InvalidLengthErr")
+    each = mode == ffi.POINTS_MUL_EACH
+    bufs = []
+    try:
+        d = _stage_bytes(lib, h)
+        bufs.append(d)
+        d_sc = d_add = None
+        if each:
+            d_sc = _stage_bytes(lib, sc)
+            bufs.append(d_sc)
+        if add is not None:
+            d_add = _stage_bytes(lib, add)
+            bufs.append(d_add)
+        ffi.check(lib.panda_points_scalar_mul(curve, mode, d, d_sc, None if each else _ptr(sc), d_add, d, n, gm.exec_stream.raw), "SchedulingErr")
+        out = np.empty(h.size, np.uint8)
+        ffi.check(lib.panda_memcpy(_ptr(out), d, h.size), "CreateContextError")
+    finally:
+        for b in bufs:
+            lib.panda_free(b)
+    return out.reshape(n, pb)
+
+
+class PandaKzgOpenAll:
+    """Additive: KZG proofs of a polynomial at ALL n points of its domain (Feist-Khovratovich) against one SRS.  `srs` holds the n = 2^k
+    affine G1 points [tau^i]G (the MSM's base wire form), `omega2` a primitive 2n-th root of unity (one Montgomery-form scalar, 32 B); the
+    proofs are for the domain omega^j with omega = omega2^2.  The constructor runs panda_kzg_open_all_setup once and keeps the table of
+    2n points and the workspace resident; open(coeffs) is one panda_kzg_open_all call; close() frees the device memory."""
+
+    def __init__(self, gm: PandaGpuManager, srs, omega2, curve: int = BN254):
+        lib = ffi.load()
+        self.gm, self.curve, self.pb = gm, curve, _POINT_BYTES[curve]
+        h = _as_bytes(srs)
+        n = h.size // self.pb
+        self.omega2 = _as_bytes(omega2).copy()
+        if n < 2 or n & (n - 1) or n * self.pb != h.size or self.omega2.size != FIELD_ELEMENT_LEN:
+            raise PandaGpuError("InvalidLengthErr")
+        self.n, self.log_n = n, log_2(n)
+        work = C.c_size_t(0)
+        ffi.check(lib.panda_kzg_open_all_plan(curve, self.log_n, C.byref(work), None), "InvalidLengthErr")
+        self.work_bytes = work.value
+        self.d_table, self.d_work, self.d_proofs = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        d_srs = None
+        try:
+            ffi.check(lib.panda_malloc(C.byref(self.d_table), 2 * n * self.pb), "CreateContextError")
+            ffi.check(lib.panda_malloc(C.byref(self.d_work), self.work_bytes), "CreateContextError")
+            ffi.check(lib.panda_malloc(C.byref(self.d_proofs), n * self.pb), "CreateContextError")
+            d_srs = _stage_bytes(lib, h)
+            ffi.check(lib.panda_kzg_open_all_setup(curve, d_srs, self.log_n, _ptr(self.omega2), self.d_table, gm.exec_stream.raw), "SchedulingErr")
+        except PandaGpuError:
+            self.close()
+            raise
+        finally:
+            if d_srs:
+                lib.panda_free(d_srs)
+
+    def open(self, coeffs) -> np.ndarray:
+        """n Montgomery-form coefficients (32 B each) -> (n, point bytes) uint8: proof j opens the polynomial at omega^j"""
+        lib = ffi.load()
+        c = _as_bytes(coeffs)
+        if c.size != self.n * FIELD_ELEMENT_LEN or not self.d_table:
+            raise PandaGpuError("InvalidLengthErr")
+        d_c = _stage_bytes(lib, c)
+        try:
+            ffi.check(lib.panda_kzg_open_all(self.curve, d_c, self.d_table, self.log_n, _ptr(self.omega2), self.d_work, self.work_bytes, self.d_proofs,
+                                             self.gm.exec_stream.raw), "SchedulingErr")
+            out = np.empty(self.n * self.pb, np.uint8)
+            ffi.check(lib.panda_memcpy(_ptr(out), self.d_proofs, out.size), "CreateContextError")
+        finally:
+            lib.panda_free(d_c)
+        return out.reshape(self.n, self.pb)
+
+    def close(self):
+        lib = ffi.load()
+        for name in ("d_table", "d_work", "d_proofs"):
+            d = getattr(self, name)
+            if d:
+                lib.panda_free(d)
+            setattr(self, name, C.c_void_p())
