@@ -61,6 +61,36 @@ PANDA_HD unsigned uniform_stages(unsigned log_n)
     return c;
 }
 
+// workgroups of a normalisation over n points
+PANDA_HD u64 norm_blocks(u64 n)
+{
+    const u64 chunks = (n + CHUNK - 1) / CHUNK;
+    return (chunks + NORM_THREADS - 1) / NORM_THREADS;
+}
+
+// internal form -> the integer's words: a product by the integer 1, fe_reduce_once, fe_pack
+template <class Fr>
+PANDA_HD void scalar_from_internal(u32 (&w)[SCALAR_WORDS], const Fe<Fr> &a)
+{
+    Fe<Fr> unit, t;
+    panda29::fe_zero(unit);
+    unit.l[0] = 1;
+    panda29::fe_mul(t, a, unit);
+    panda29::fe_reduce_once(t);
+    panda29::fe_pack(w, t);
+}
+
+// host: a (internal form) has order exactly 2^k, k >= 1: a^(2^(k - 1)) == -1
+template <class Fr>
+inline bool order_is_pow2(const Fe<Fr> &a, unsigned k)
+{
+    Fe<Fr> t = a, one, sum;
+    for (unsigned i = 0; i + 1 < k; i++) panda29::fe_sqr(t, t);
+    panda29::fe_one(one);
+    panda29::fe_add(sum, t, one);
+    return panda29::fe_is_zero_mod_p(sum);
+}
+
 // the two points and the twiddle of butterfly t < n / 2 in stage s (span 2^s): twiddle-major, so that consecutive t share w
 struct ButterflyIndex {
     u32 lo, hi, twiddle; // x[lo], x[hi], table index of w = omega^twiddle

@@ -1,6 +1,7 @@
 // ec_ntt.hip -- the discrete Fourier transform over G1 points (panda_ec_ntt, panda_ec_ntt_plan) and the batch conversion of MSM result
 // triples to affine points (panda_points_to_affine, panda_points_to_affine_plan); DESIGN.md 5.9.  ec_ntt.h holds what a thread computes,
-// the bounds and the treatment of the exceptional cases; this file holds the kernels and the host side.
+// the bounds and the treatment of the exceptional cases, point_vec.h the point loads and stores shared with points_mul.hip; this file
+// holds the kernels and the host side.
 //
 // A transform of n = 2^log_n points runs, on the caller's stream:
 //   k_twiddles     log_n >= 2: the n / 2 canonical (plain-integer) powers of the root, 32 B each, into scratch.  Built by every call: a
@@ -11,7 +12,8 @@
 //                  readfirstlane, so they and every branch on them are scalar.  k_stage<F, false> runs the other stages.
 //   k_scale        inverse only: every point times n^-1, one scalar for the launch (uniform everywhere)
 //   k_normalise    XYZZ -> affine wire points in d_out, one inversion per CHUNK points (ec_ntt.h normalise_chunk); the prefix products
-//                  are parked in the output slots themselves, so the normalisation needs no scratch of its own
+//                  are parked in the output slots themselves, so the normalisation needs no scratch of its own.  Compiled here only:
+//                  points_mul.hip reaches it through enqueue_normalise (point_vec.h)
 // No kernel waits for another workgroup and there are no atomics; every launch is ordered by the stream.  The stage kernels are one wave
 // per workgroup (__launch_bounds__(64)): the 14-limb butterfly takes the 256 VGPRs, keeps a few values in AGPRs and needs no scratch memory.
 // The intermediate points and the table live in the calling thread's arena (released by panda_ntt_tear_down).
@@ -20,6 +22,7 @@
 #include "ec_ntt.h"
 #include "fe29.h"
 #include "panda_internal.h"
+#include "point_vec.h"
 #include "poly_elem.h"
 
 using namespace panda29;
@@ -28,57 +31,6 @@ using panda_poly::ranges_overlap;
 using panda_poly::take_scratch;
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------- loads and stores
-// n32 u32 words, 16-byte aligned on both sides
-template <int WORDS>
-__device__ __forceinline__ void copy_words_in(u32 *dst, const u32 *__restrict__ src)
-{
-    static_assert(WORDS % 4 == 0, "whole uint4s");
-    const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-#pragma unroll
-    for (int i = 0; i < WORDS / 4; i++) {
-        const uint4 v = s4[i];
-        dst[4 * i] = v.x, dst[4 * i + 1] = v.y, dst[4 * i + 2] = v.z, dst[4 * i + 3] = v.w;
-    }
-}
-template <int WORDS>
-__device__ __forceinline__ void copy_words_out(u32 *__restrict__ dst, const u32 *src)
-{
-    static_assert(WORDS % 4 == 0, "whole uint4s");
-    uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-#pragma unroll
-    for (int i = 0; i < WORDS / 4; i++) d4[i] = make_uint4(src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]);
-}
-
-// a scratch point is the four elements' limbs as they stand: 4 N words
-template <class F>
-__device__ __forceinline__ void load_point(Xyzz<F> &p, const u32 *__restrict__ pts, u64 i)
-{
-    constexpr int N = F::N;
-    u32 w[4 * N];
-    copy_words_in<4 * N>(w, pts + i * (4 * N));
-#pragma unroll
-    for (int k = 0; k < N; k++) p.X.l[k] = w[k], p.Y.l[k] = w[N + k], p.ZZ.l[k] = w[2 * N + k], p.ZZZ.l[k] = w[3 * N + k];
-}
-template <class F>
-__device__ __forceinline__ void store_point(u32 *__restrict__ pts, u64 i, const Xyzz<F> &p)
-{
-    constexpr int N = F::N;
-    u32 w[4 * N];
-#pragma unroll
-    for (int k = 0; k < N; k++) w[k] = p.X.l[k], w[N + k] = p.Y.l[k], w[2 * N + k] = p.ZZ.l[k], w[3 * N + k] = p.ZZZ.l[k];
-    copy_words_out<4 * N>(pts + i * (4 * N), w);
-}
-
-template <class F>
-__device__ __forceinline__ void load_affine(Xyzz<F> &p, const u32 *__restrict__ wire, u64 i)
-{
-    constexpr int L = F::L;
-    u32 w[2 * L];
-    copy_words_in<2 * L>(w, wire + i * (2 * L));
-    point_from_affine_wire(p, w);
-}
 
 struct ScalarWords {
     u32 w[SCALAR_WORDS];
@@ -96,19 +48,15 @@ __global__ void __launch_bounds__(256) k_twiddles(u32 *__restrict__ table, u32 h
 {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i >= half) return;
-    Fe<Fr> acc, t, unit;
+    Fe<Fr> acc, t;
     fe_one(acc);
 #pragma unroll
     for (int b = 0; b < (int)MAX_LOG_N - 1; b++) { // statically indexed; i < 2^25
         fe_mul(t, acc, rp.sq[b]);
         fe_select(acc, ((i >> b) & 1u) != 0, t, acc);
     }
-    fe_zero(unit);
-    unit.l[0] = 1;
-    fe_mul(t, acc, unit); // internal -> the integer itself
-    fe_reduce_once(t);
     u32 w[SCALAR_WORDS];
-    fe_pack(w, t);
+    scalar_from_internal(w, acc);
     copy_words_out<SCALAR_WORDS>(table + (u64)i * SCALAR_WORDS, w);
 }
 
@@ -163,12 +111,37 @@ __global__ void __launch_bounds__(STAGE_THREADS) k_scale(u32 *pts, u32 n, const 
     store_point(pts, i, r);
 }
 
-// the accesses of normalise_chunk over scratch points; `first` is the chunk's first point, every index below n by the caller's count
+// the output side of normalise_chunk's accesses: `first` is the chunk's first point, every index below n by the caller's count.  A
+// prefix product is parked in the point's own output slot (point_vec.h asserts that it fits).
 template <class F>
-struct XyzzChunk {
-    const u32 *__restrict__ pts;
+struct OutSlots {
     u32 *__restrict__ out;
     u64 first;
+    __device__ __forceinline__ void put_prefix(u32 i, const Fe<F> &v) const
+    {
+        u32 *dst = out + (first + i) * (2 * F::L);
+#pragma unroll
+        for (int k = 0; k < F::N; k++) dst[k] = v.l[k];
+    }
+    __device__ __forceinline__ void get_prefix(Fe<F> &v, u32 i) const
+    {
+        const u32 *src = out + (first + i) * (2 * F::L);
+#pragma unroll
+        for (int k = 0; k < F::N; k++) v.l[k] = src[k];
+    }
+    __device__ __forceinline__ void put_identity(u32 i) const
+    {
+        u32 w[2 * F::L] = {};
+        copy_words_out<2 * F::L>(out + (first + i) * (2 * F::L), w);
+    }
+};
+
+// the accesses of normalise_chunk over scratch points
+template <class F>
+struct XyzzChunk : OutSlots<F> {
+    const u32 *__restrict__ pts;
+    using OutSlots<F>::first;
+    using OutSlots<F>::out;
     __device__ __forceinline__ bool denominator(Fe<F> &d, u32 i) const
     {
         constexpr int N = F::N;
@@ -178,18 +151,6 @@ struct XyzzChunk {
         for (int k = 0; k < N; k++) nz |= src[2 * N + k], d.l[k] = src[3 * N + k];
         return nz != 0;
     }
-    __device__ __forceinline__ void put_prefix(u32 i, const Fe<F> &v) const
-    {
-        u32 *dst = out + (first + i) * (2 * F::L);
-#pragma unroll
-        for (int k = 0; k < F::N; k++) dst[k] = v.l[k];
-    }
-    __device__ __forceinline__ void get_prefix(Fe<F> &v, u32 i) const
-    {
-        const u32 *src = out + (first + i) * (2 * F::L);
-#pragma unroll
-        for (int k = 0; k < F::N; k++) v.l[k] = src[k];
-    }
     __device__ __forceinline__ void finish(u32 i, const Fe<F> &dinv) const
     {
         Xyzz<F> p;
@@ -198,37 +159,20 @@ struct XyzzChunk {
         xyzz_affine_wire(w, p, dinv);
         copy_words_out<2 * F::L>(out + (first + i) * (2 * F::L), w);
     }
-    __device__ __forceinline__ void put_identity(u32 i) const
-    {
-        u32 w[2 * F::L] = {};
-        copy_words_out<2 * F::L>(out + (first + i) * (2 * F::L), w);
-    }
 };
 
 // the same over X || Y || Z wire triples
 template <class F>
-struct TripleChunk {
+struct TripleChunk : OutSlots<F> {
     const u32 *__restrict__ in;
-    u32 *__restrict__ out;
-    u64 first;
     bool homogeneous;
+    using OutSlots<F>::first;
+    using OutSlots<F>::out;
     __device__ __forceinline__ bool denominator(Fe<F> &d, u32 i) const
     {
         u32 z[F::L];
         copy_words_in<F::L>(z, in + (first + i) * (3 * F::L) + 2 * F::L);
         return triple_denominator<F>(d, z);
-    }
-    __device__ __forceinline__ void put_prefix(u32 i, const Fe<F> &v) const
-    {
-        u32 *dst = out + (first + i) * (2 * F::L);
-#pragma unroll
-        for (int k = 0; k < F::N; k++) dst[k] = v.l[k];
-    }
-    __device__ __forceinline__ void get_prefix(Fe<F> &v, u32 i) const
-    {
-        const u32 *src = out + (first + i) * (2 * F::L);
-#pragma unroll
-        for (int k = 0; k < F::N; k++) v.l[k] = src[k];
     }
     __device__ __forceinline__ void finish(u32 i, const Fe<F> &dinv) const
     {
@@ -237,21 +181,14 @@ struct TripleChunk {
         triple_affine_wire<F>(w, t, dinv, homogeneous);
         copy_words_out<2 * F::L>(out + (first + i) * (2 * F::L), w);
     }
-    __device__ __forceinline__ void put_identity(u32 i) const
-    {
-        u32 w[2 * F::L] = {};
-        copy_words_out<2 * F::L>(out + (first + i) * (2 * F::L), w);
-    }
 };
-
-static_assert(2 * Bn254Fq::L >= Bn254Fq::N && 2 * Bls377Fq::L >= Bls377Fq::N && 2 * Bls381Fq::L >= Bls381Fq::N, "an output slot holds a prefix product");
 
 template <class F>
 __global__ void __launch_bounds__(NORM_THREADS) k_normalise(const u32 *__restrict__ pts, u32 *__restrict__ out, u64 n)
 {
     const u64 first = ((u64)blockIdx.x * NORM_THREADS + threadIdx.x) * CHUNK;
     if (first >= n) return;
-    XyzzChunk<F> io = {pts, out, first};
+    XyzzChunk<F> io = {{out, first}, pts};
     normalise_chunk<F>(io, n - first < CHUNK ? (u32)(n - first) : CHUNK);
 }
 
@@ -260,25 +197,11 @@ __global__ void __launch_bounds__(NORM_THREADS) k_normalise_triples(const u32 *_
 {
     const u64 first = ((u64)blockIdx.x * NORM_THREADS + threadIdx.x) * CHUNK;
     if (first >= n) return;
-    TripleChunk<F> io = {in, out, first, homogeneous};
+    TripleChunk<F> io = {{out, first}, in, homogeneous};
     normalise_chunk<F>(io, n - first < CHUNK ? (u32)(n - first) : CHUNK);
 }
 
 // ------------------------------------------------------------------------------------------------- the host side
-// f(Fq(), Fr()) for a G1 curve id; the entry points refuse curve > 2 before they get here
-template <class Fn>
-inline auto with_curve(unsigned curve, Fn &&f)
-{
-    switch (curve) {
-    case 0: return f(Bn254Fq(), Bn254Fr());
-    case 1: return f(Bls377Fq(), Bls377Fr());
-    default: return f(Bls381Fq(), Bls381Fr());
-    }
-}
-
-size_t affine_bytes(unsigned curve) { return curve == 0 ? 64 : 96; }
-size_t xyzz_bytes(unsigned curve) { return curve == 0 ? 4 * 9 * 4 : 4 * 14 * 4; }
-
 unsigned ntt_launches(unsigned log_n, unsigned direction)
 {
     if (log_n == 0) return 2;
@@ -288,18 +211,6 @@ size_t ntt_scratch_bytes(unsigned curve, unsigned log_n)
 {
     const size_t n = (size_t)1 << log_n;
     return panda::align256(n * xyzz_bytes(curve)) + panda::align256((n / 2 ? n / 2 : 1) * 4 * SCALAR_WORDS) + 2 * 256;
-}
-
-// internal form -> the integer's words
-template <class Fr>
-void canonical_words(u32 (&w)[SCALAR_WORDS], const Fe<Fr> &a)
-{
-    Fe<Fr> unit, t;
-    fe_zero(unit);
-    unit.l[0] = 1;
-    fe_mul(t, a, unit);
-    fe_reduce_once(t);
-    fe_pack(w, t);
 }
 
 // the forward root of a transform of 2^log_n points: below the modulus, and for log_n >= 1 of order exactly 2^log_n
@@ -312,15 +223,11 @@ bool root_valid(const u32 *omega_wire, unsigned log_n, Fe<Fr> &root)
     }
     if (!panda_poly::wire_below_modulus<Fr>(omega_wire)) return false;
     fe_from_wire(root, omega_wire);
-    Fe<Fr> t = root, one, sum;
-    for (unsigned i = 0; i + 1 < log_n; i++) fe_sqr(t, t);
-    fe_one(one);
-    fe_add(sum, t, one); // root^(n / 2) + 1
-    return fe_is_zero_mod_p(sum);
+    return order_is_pow2(root, log_n); // root^(n / 2) == -1
 }
 
 template <class F, class Fr>
-hipError_t run_ec_ntt(hipStream_t stream, const void *d_in, void *d_out, unsigned log_n, bool inverse, const Fe<Fr> &omega)
+hipError_t run_ec_ntt(unsigned curve, hipStream_t stream, const void *d_in, void *d_out, unsigned log_n, bool inverse, const Fe<Fr> &omega)
 {
     PANDA_TRY(panda::order_after_null_stream(stream));
     const u32 n = (u32)1 << log_n, half = n / 2;
@@ -355,13 +262,11 @@ hipError_t run_ec_ntt(hipStream_t stream, const void *d_in, void *d_out, unsigne
         fe_from_u32(nf, n);
         fe_inv(ninv, nf);
         ScalarWords k;
-        canonical_words(k.w, ninv);
+        scalar_from_internal(k.w, ninv);
         hipLaunchKernelGGL((k_scale<F>), dim3((n + STAGE_THREADS - 1) / STAGE_THREADS), dim3(STAGE_THREADS), 0, stream, pts, n, k);
         PANDA_TRY(hipGetLastError());
     }
-    const u32 chunks = (n + CHUNK - 1) / CHUNK;
-    hipLaunchKernelGGL((k_normalise<F>), dim3((chunks + NORM_THREADS - 1) / NORM_THREADS), dim3(NORM_THREADS), 0, stream, (const u32 *)pts, (u32 *)d_out, (u64)n);
-    PANDA_TRY(hipGetLastError());
+    PANDA_TRY(enqueue_normalise(curve, stream, pts, (u32 *)d_out, n));
     return hipStreamSynchronize(stream);
 }
 
@@ -369,14 +274,20 @@ template <class F>
 hipError_t run_to_affine(hipStream_t stream, const void *d_in, void *d_out, u64 n, bool homogeneous)
 {
     PANDA_TRY(panda::order_after_null_stream(stream));
-    const u64 chunks = (n + CHUNK - 1) / CHUNK;
-    hipLaunchKernelGGL((k_normalise_triples<F>), dim3((unsigned)((chunks + NORM_THREADS - 1) / NORM_THREADS)), dim3(NORM_THREADS), 0, stream, (const u32 *)d_in,
-                       (u32 *)d_out, n, homogeneous);
+    hipLaunchKernelGGL((k_normalise_triples<F>), dim3((unsigned)norm_blocks(n)), dim3(NORM_THREADS), 0, stream, (const u32 *)d_in, (u32 *)d_out, n, homogeneous);
     PANDA_TRY(hipGetLastError());
     return hipStreamSynchronize(stream);
 }
 
 } // namespace
+
+hipError_t panda_ecntt::enqueue_normalise(unsigned curve, hipStream_t stream, const u32 *pts, u32 *out, u64 n)
+{
+    return with_curve(curve, [&](auto fq, auto) {
+        hipLaunchKernelGGL((k_normalise<decltype(fq)>), dim3((unsigned)norm_blocks(n)), dim3(NORM_THREADS), 0, stream, pts, out, n);
+        return hipGetLastError();
+    });
+}
 
 extern "C" {
 
@@ -395,7 +306,7 @@ panda_error panda_ec_ntt(unsigned curve, const void *d_in, void *d_out, unsigned
         if (log_n > 0) memcpy(w, omega, sizeof w);
         Fe<Fr> root;
         if (!root_valid<Fr>(w, log_n, root)) return panda_error_invalid_value;
-        return static_cast<panda_error>(run_ec_ntt<F, Fr>(s, d_in, d_out, log_n, direction == PANDA_EC_NTT_INVERSE, root));
+        return static_cast<panda_error>(run_ec_ntt<F, Fr>(curve, s, d_in, d_out, log_n, direction == PANDA_EC_NTT_INVERSE, root));
     });
 }
 

@@ -16,9 +16,11 @@
 #include "ec_ntt.h"
 #include "fe29.h"
 #include "panda_internal.h"
+#include "point_vec.h"
 #include "poly_elem.h"
 
 using namespace panda29;
+using panda_ecntt::affine_bytes;
 using panda_ecntt::SCALAR_WORDS;
 using panda_poly::ranges_overlap;
 typedef uint64_t u64;
@@ -58,7 +60,6 @@ __global__ void __launch_bounds__(COPY_THREADS) k_take_middle(const uint4 *__res
     for (int v = 0; v < V; v++) proofs[m * V + v] = m + 1 < n ? conv[(n - 1 + m) * V + v] : make_uint4(0, 0, 0, 0);
 }
 
-size_t affine_bytes(unsigned curve) { return curve == 0 ? 64 : 96; }
 size_t work_bytes_of(unsigned curve, unsigned log_n) { return panda::align256(((size_t)2 << log_n) * (32 + affine_bytes(curve))); }
 unsigned copy_blocks(u64 items) { return (unsigned)((items + COPY_THREADS - 1) / COPY_THREADS); }
 
@@ -69,14 +70,11 @@ bool roots_valid(unsigned curve, const void *omega2, unsigned log_n, u32 (&w2)[S
     return panda_poly::with_field(curve, [&](auto fr) {
         typedef decltype(fr) Fr;
         if (!panda_poly::wire_below_modulus<Fr>(w2)) return false;
-        Fe<Fr> root, t, one, sum;
+        Fe<Fr> root, t;
         fe_from_wire(root, w2);
         fe_sqr(t, root);
         fe_to_wire(w, t);
-        for (unsigned i = 1; i < log_n; i++) fe_sqr(t, t); // omega2^n
-        fe_one(one);
-        fe_add(sum, t, one);
-        return fe_is_zero_mod_p(sum);
+        return panda_ecntt::order_is_pow2(root, log_n + 1); // omega2^n == -1
     });
 }
 

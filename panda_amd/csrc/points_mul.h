@@ -21,6 +21,8 @@ namespace panda_pmul {
 using panda29::Fe;
 using panda29::u32;
 using panda29::Xyzz;
+using panda_ecntt::norm_blocks; // workgroups of the normalisation over n points
+using panda_ecntt::scalar_from_internal;
 using panda_ecntt::SCALAR_WORDS;
 typedef uint64_t u64;
 
@@ -29,13 +31,8 @@ using panda_ecntt::MAX_POINTS;              // n of one call: 2^28, the cap of t
 constexpr int POWER_BITS = 28;              // bits of an index below MAX_POINTS
 constexpr unsigned MODE_EACH = 0, MODE_ONE = 1, MODE_POWERS = 2; // PANDA_POINTS_MUL_*
 
-// workgroups of the multiplication kernel and of the normalisation over n points
+// workgroups of the multiplication kernel over n points
 PANDA_HD u64 mul_blocks(u64 n) { return (n + MUL_THREADS - 1) / MUL_THREADS; }
-PANDA_HD u64 norm_blocks(u64 n)
-{
-    const u64 chunks = (n + panda_ecntt::CHUNK - 1) / panda_ecntt::CHUNK;
-    return (chunks + panda_ecntt::NORM_THREADS - 1) / panda_ecntt::NORM_THREADS;
-}
 
 // significant bits of the integer in SCALAR_WORDS little-endian words: 0 for zero, 256 for a set top bit
 PANDA_HD unsigned scalar_bits(const u32 (&w)[SCALAR_WORDS])
@@ -85,18 +82,6 @@ template <class Fr>
 PANDA_HD void scalar_from_wire(u32 (&w)[SCALAR_WORDS], const u32 *wire)
 {
     panda29::fe_wire_to_canonical<Fr>(w, wire);
-}
-
-// internal form -> the integer's words (ec_ntt.hip k_twiddles: a product by the integer 1, fe_reduce_once, fe_pack)
-template <class Fr>
-PANDA_HD void scalar_from_internal(u32 (&w)[SCALAR_WORDS], const Fe<Fr> &a)
-{
-    Fe<Fr> unit, t;
-    panda29::fe_zero(unit);
-    unit.l[0] = 1;
-    panda29::fe_mul(t, a, unit);
-    panda29::fe_reduce_once(t);
-    panda29::fe_pack(w, t);
 }
 
 // c, s^(2^b) for b < POWER_BITS, internal form: the by-value table of POWERS

@@ -6,15 +6,17 @@
 //   k_points_mul<F, Fr, MODE, ADD>   point i: the integer k_i (EACH: the wire residue taken to the integer; ONE: the words by value;
 //                                    POWERS: c s^i from the by-value table), the wave's longest bit count, k_i P_i over that many
 //                                    steps, + A_i with ADD; the XYZZ point goes to arena scratch
-//   k_points_normalise<F>            XYZZ -> affine wire points in d_out, one inversion per CHUNK points (ec_ntt.h normalise_chunk)
+//   k_normalise<F>                   of ec_ntt.hip through enqueue_normalise: XYZZ -> affine wire points in d_out, one inversion per
+//                                    CHUNK points (ec_ntt.h normalise_chunk)
 // d_out is written by the second launch only, after every input has been read: it may be d_points or d_addend.  One wave per workgroup
 // in the first kernel; no kernel waits for another workgroup, there are no atomics and no LDS.  In ONE mode the words are kernel
 // arguments, so they and every branch on them are scalar; in EACH and POWERS a wave pays the doubling and the addition for every step.
-// The point loads and stores and the normalisation's accessors repeat those of ec_ntt.hip, whose kernels are left as they are.
+// The point loads and stores, the sizes and the curve dispatch are point_vec.h's, shared with ec_ntt.hip.
 #include <string.h>
 
 #include "fe29.h"
 #include "panda_internal.h"
+#include "point_vec.h"
 #include "points_mul.h"
 #include "poly_elem.h"
 
@@ -25,47 +27,6 @@ using panda_poly::ranges_overlap;
 using panda_poly::take_scratch;
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------- loads and stores
-template <int WORDS>
-__device__ __forceinline__ void copy_words_in(u32 *dst, const u32 *src)
-{
-    static_assert(WORDS % 4 == 0, "whole uint4s");
-    const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-#pragma unroll
-    for (int i = 0; i < WORDS / 4; i++) {
-        const uint4 v = s4[i];
-        dst[4 * i] = v.x, dst[4 * i + 1] = v.y, dst[4 * i + 2] = v.z, dst[4 * i + 3] = v.w;
-    }
-}
-template <int WORDS>
-__device__ __forceinline__ void copy_words_out(u32 *dst, const u32 *src)
-{
-    static_assert(WORDS % 4 == 0, "whole uint4s");
-    uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-#pragma unroll
-    for (int i = 0; i < WORDS / 4; i++) d4[i] = make_uint4(src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]);
-}
-
-// a scratch point is the four elements' limbs as they stand: 4 N words
-template <class F>
-__device__ __forceinline__ void load_point(Xyzz<F> &p, const u32 *pts, u64 i)
-{
-    constexpr int N = F::N;
-    u32 w[4 * N];
-    copy_words_in<4 * N>(w, pts + i * (4 * N));
-#pragma unroll
-    for (int k = 0; k < N; k++) p.X.l[k] = w[k], p.Y.l[k] = w[N + k], p.ZZ.l[k] = w[2 * N + k], p.ZZZ.l[k] = w[3 * N + k];
-}
-template <class F>
-__device__ __forceinline__ void store_point(u32 *pts, u64 i, const Xyzz<F> &p)
-{
-    constexpr int N = F::N;
-    u32 w[4 * N];
-#pragma unroll
-    for (int k = 0; k < N; k++) w[k] = p.X.l[k], w[N + k] = p.Y.l[k], w[2 * N + k] = p.ZZ.l[k], w[3 * N + k] = p.ZZZ.l[k];
-    copy_words_out<4 * N>(pts + i * (4 * N), w);
-}
 
 // ------------------------------------------------------------------------------------------------- kernels
 // what a mode passes by value
@@ -95,7 +56,6 @@ template <class F, class Fr, unsigned MODE, bool ADD>
 __global__ void __launch_bounds__(MUL_THREADS) k_points_mul(const u32 *__restrict__ points, const u32 *__restrict__ scalars, const u32 *__restrict__ addend,
                                                             u32 *__restrict__ pts, u64 n, const MulArgs<Fr, MODE> args)
 {
-    constexpr int L = F::L;
     const u64 i = (u64)blockIdx.x * MUL_THREADS + threadIdx.x;
     const bool live = i < n; // the last wave's tail runs the loop with k = 0 over the identity and stores nothing
     u32 k[SCALAR_WORDS] = {};
@@ -117,86 +77,18 @@ __global__ void __launch_bounds__(MUL_THREADS) k_points_mul(const u32 *__restric
     }
     Xyzz<F> p, acc;
     xyzz_set_identity(p);
-    if (live) {
-        u32 w[2 * L];
-        copy_words_in<2 * L>(w, points + i * (2 * L));
-        point_from_affine_wire(p, w);
-    }
+    if (live) load_affine(p, points, i);
     panda_pmul::scalar_mul(acc, p, k, bits);
     if (!live) return;
     if constexpr (ADD) {
-        u32 w[2 * L];
-        copy_words_in<2 * L>(w, addend + i * (2 * L));
+        u32 w[2 * F::L];
+        copy_words_in<2 * F::L>(w, addend + i * (2 * F::L));
         add_affine_wire(acc, w);
     }
     store_point(pts, i, acc);
 }
 
-// the accesses of normalise_chunk over scratch points; `first` is the chunk's first point, every index below n by the caller's count
-template <class F>
-struct XyzzChunk {
-    const u32 *__restrict__ pts;
-    u32 *__restrict__ out;
-    u64 first;
-    __device__ __forceinline__ bool denominator(Fe<F> &d, u32 i) const
-    {
-        constexpr int N = F::N;
-        const u32 *src = pts + (first + i) * (4 * N);
-        u32 nz = 0;
-#pragma unroll
-        for (int k = 0; k < N; k++) nz |= src[2 * N + k], d.l[k] = src[3 * N + k];
-        return nz != 0;
-    }
-    __device__ __forceinline__ void put_prefix(u32 i, const Fe<F> &v) const
-    {
-        u32 *dst = out + (first + i) * (2 * F::L);
-#pragma unroll
-        for (int k = 0; k < F::N; k++) dst[k] = v.l[k];
-    }
-    __device__ __forceinline__ void get_prefix(Fe<F> &v, u32 i) const
-    {
-        const u32 *src = out + (first + i) * (2 * F::L);
-#pragma unroll
-        for (int k = 0; k < F::N; k++) v.l[k] = src[k];
-    }
-    __device__ __forceinline__ void finish(u32 i, const Fe<F> &dinv) const
-    {
-        Xyzz<F> p;
-        load_point(p, pts, first + i);
-        u32 w[2 * F::L];
-        xyzz_affine_wire(w, p, dinv);
-        copy_words_out<2 * F::L>(out + (first + i) * (2 * F::L), w);
-    }
-    __device__ __forceinline__ void put_identity(u32 i) const
-    {
-        u32 w[2 * F::L] = {};
-        copy_words_out<2 * F::L>(out + (first + i) * (2 * F::L), w);
-    }
-};
-static_assert(2 * Bn254Fq::L >= Bn254Fq::N && 2 * Bls377Fq::L >= Bls377Fq::N && 2 * Bls381Fq::L >= Bls381Fq::N, "an output slot holds a prefix product");
-
-template <class F>
-__global__ void __launch_bounds__(NORM_THREADS) k_points_normalise(const u32 *__restrict__ pts, u32 *__restrict__ out, u64 n)
-{
-    const u64 first = ((u64)blockIdx.x * NORM_THREADS + threadIdx.x) * CHUNK;
-    if (first >= n) return;
-    XyzzChunk<F> io = {pts, out, first};
-    normalise_chunk<F>(io, n - first < CHUNK ? (u32)(n - first) : CHUNK);
-}
-
 // ------------------------------------------------------------------------------------------------- the host side
-template <class Fn>
-inline auto with_curve(unsigned curve, Fn &&f)
-{
-    switch (curve) {
-    case 0: return f(Bn254Fq(), Bn254Fr());
-    case 1: return f(Bls377Fq(), Bls377Fr());
-    default: return f(Bls381Fq(), Bls381Fr());
-    }
-}
-
-size_t affine_bytes(unsigned curve) { return curve == 0 ? 64 : 96; }
-size_t xyzz_bytes(unsigned curve) { return curve == 0 ? 4 * 9 * 4 : 4 * 14 * 4; }
 bool shape_invalid(unsigned curve, unsigned mode, u64 n) { return curve > 2 || mode > MODE_POWERS || n == 0 || n > MAX_POINTS; }
 
 template <class F, class Fr, unsigned MODE>
@@ -212,8 +104,8 @@ hipError_t launch_mul(hipStream_t stream, const void *d_points, const void *d_sc
 
 // h: the host scalars of the mode in internal form (ONE: h[0]; POWERS: h[0] = c, h[1] = s)
 template <class F, class Fr>
-hipError_t run_points_mul(hipStream_t stream, unsigned mode, const void *d_points, const void *d_scalars, const Fe<Fr> (&h)[2], const void *d_addend, void *d_out,
-                          u64 n)
+hipError_t run_points_mul(unsigned curve, hipStream_t stream, unsigned mode, const void *d_points, const void *d_scalars, const Fe<Fr> (&h)[2], const void *d_addend,
+                          void *d_out, u64 n)
 {
     PANDA_TRY(panda::order_after_null_stream(stream));
     void *block[1];
@@ -230,12 +122,9 @@ hipError_t run_points_mul(hipStream_t stream, unsigned mode, const void *d_point
         power_table(a.table, h[0], h[1]);
         PANDA_TRY((launch_mul<F, Fr, MODE_POWERS>(stream, d_points, nullptr, d_addend, pts, n, a)));
     }
-    hipLaunchKernelGGL((k_points_normalise<F>), dim3((unsigned)norm_blocks(n)), dim3(NORM_THREADS), 0, stream, (const u32 *)pts, (u32 *)d_out, n);
-    PANDA_TRY(hipGetLastError());
+    PANDA_TRY(enqueue_normalise(curve, stream, pts, (u32 *)d_out, n));
     return hipStreamSynchronize(stream);
 }
-
-static_assert(sizeof(Xyzz<Bn254Fq>) == 144 && sizeof(Xyzz<Bls377Fq>) == 224 && sizeof(Xyzz<Bls381Fq>) == 224, "the scratch point of the plan");
 
 } // namespace
 
@@ -269,7 +158,7 @@ panda_error panda_points_scalar_mul(unsigned curve, unsigned mode, const void *d
             if (!panda_poly::wire_below_modulus<Fr>(w)) return panda_error_invalid_value;
             fe_from_wire(h[j], w);
         }
-        return static_cast<panda_error>(run_points_mul<F, Fr>(s, mode, d_points, d_scalars, h, d_addend, d_out, n));
+        return static_cast<panda_error>(run_points_mul<F, Fr>(curve, s, mode, d_points, d_scalars, h, d_addend, d_out, n));
     });
 }
 
