@@ -598,6 +598,31 @@ PANDA_HD void fe_pack(u32 *w, const Fe<F> &a)
     }
 }
 
+// r = p - w on the L packed 32-bit words of a canonical value (0 < w < p; r may be w): one borrow chain, L instructions on the device
+// (v_sub_co / v_subb_co), and the result is canonical again, so fe_unpack gives tight limbs.  w == 0 would come back as p, which is
+// not canonical: callers keep zero (the y of an identity row) away from it, or do not look at the result.
+template <class F>
+PANDA_HD void fe_words_neg(u32 *r, const u32 *w)
+{
+    static_assert(!IsExt2<F>::value, "prime fields only");
+#if defined(__clang__)
+    // the builtin is what becomes a v_sub_co / v_subb_co chain (64-bit differences become three instructions a word).  The words of p
+    // go through registers: an instruction that takes its borrow from VCC cannot take a literal as well.
+    unsigned borrow = 0;
+#pragma unroll
+    for (int i = 0; i < F::L; i++) r[i] = __builtin_subc(F::PW[i], w[i], borrow, &borrow);
+#else
+    u32 borrow = 0;
+#pragma unroll
+    for (int i = 0; i < F::L; i++) {
+        const u32 d = F::PW[i] - w[i];
+        const u32 out = (u32)(F::PW[i] < w[i]) | (u32)(d < borrow);
+        r[i] = d - borrow;
+        borrow = out;
+    }
+#endif
+}
+
 // sequential carry propagation: limb 0 < 2^32, limbs 1..N-1 <= 2^32 - 8 (a carry is at most 7 and must not wrap the limb it lands
 // on) -> tight (value unchanged)
 template <class F>

@@ -402,6 +402,27 @@ __global__ void __launch_bounds__(256) k_chunk_first(const u32 *__restrict__ off
 #ifndef PANDA_ROW_MASK
 #define PANDA_ROW_MASK 0x7fffffffu
 #endif
+// The code around the addition in the hot loop, slimmed for the 9-limb prime fields (BN254's Fq: what the built-in sorted-words-through-
+// LDS kernel runs over).  Each item can be built out for a measurement (-DPANDA_ACC_ITEMS=<mask>); the 14-limb and Fq2 kernels never
+// take any of them.
+#ifndef PANDA_ACC_ITEMS
+#define PANDA_ACC_ITEMS 0x3fu
+#endif
+constexpr unsigned ACC_ITEM_ROW_TUPLES = 32u; // the gathered row is carried to the next trip as the loads' own four-word vectors
+constexpr unsigned ACC_ITEM_WORDS_NEG = 1u;  // a negative digit's y is negated on the packed words (fe_words_neg), not limb-wise
+constexpr unsigned ACC_ITEM_Y_IDENTITY = 2u; // a row is tested for the identity on the words of y alone
+constexpr unsigned ACC_ITEM_QUAD_SHIFT = 4u; // the four sorted words of a quad are shifted down, not selected by index
+constexpr unsigned ACC_ITEM_ID_FLAG = 8u;    // "the accumulator is the identity" is a lane flag, not an OR over ZZ
+constexpr unsigned ACC_ITEM_BOUNDARY = 16u;  // one place where a row becomes the accumulator, no carry pass on its y, running bucket address
+template <class F>
+struct AccSlim {
+    static constexpr bool value = !IsExt2<F>::value && F::N <= 9;
+};
+template <class F>
+__host__ __device__ constexpr bool acc_item(unsigned item)
+{
+    return AccSlim<F>::value && (PANDA_ACC_ITEMS & item) != 0;
+}
 // a converted base as it sits in HBM: 2*L words, all zero for the identity
 template <class F>
 struct PackedBase {
@@ -418,25 +439,78 @@ __device__ __forceinline__ void fetch_base(PackedBase<F> &b, const u32 *bases, u
 #endif
 }
 
+// The row as the hot loop carries it from the trip that gathers it to the trip that unpacks it: the four-word vectors the loads
+// deliver, kept whole.  Carried as 2 L separate words the loop's registers and the loads' aligned register quadruples did not match:
+// the compiled loop waited for the row right behind the gather (s_waitcnt vmcnt(0)) and moved 15 of its 16 words, all before the
+// addition it was meant to travel under.
+template <class F>
+struct PackedRow {
+    typedef u32 v4u __attribute__((ext_vector_type(4)));
+    v4u q[2 * F::L / 4];
+};
+template <class F>
+__device__ __forceinline__ void fetch_row(PackedRow<F> &r, const u32 *bases, u32 entry)
+{
+    typedef typename PackedRow<F>::v4u v4u;
+    const v4u *s4 = reinterpret_cast<const v4u *>(bases + (u64)(entry & PANDA_ROW_MASK) * 2 * F::L);
+#pragma unroll
+    for (int j = 0; j < 2 * F::L / 4; j++) {
+#if defined(PANDA_ROWS_NT)
+        r.q[j] = __builtin_nontemporal_load(&s4[j]);
+#else
+        r.q[j] = s4[j];
+#endif
+    }
+}
+template <class F>
+__device__ __forceinline__ void row_words(PackedBase<F> &b, const PackedRow<F> &r)
+{
+#pragma unroll
+    for (int j = 0; j < 2 * F::L / 4; j++) {
+        b.w[4 * j] = r.q[j].x;
+        b.w[4 * j + 1] = r.q[j].y;
+        b.w[4 * j + 2] = r.q[j].z;
+        b.w[4 * j + 3] = r.q[j].w;
+    }
+}
+
 // RAW: a negated y comes back un-normalised (limbs < 2^31) -- good enough for the one product it feeds in
 // xyzz_madd_core, three instructions per limb cheaper; callers that store or square y normalise it first
-template <class F, bool RAW = false>
+// SLIM: the spelling of accumulate_chunk's loop (items 1 and 2 below); every other caller -- k_accumulate_shared, the table kernels --
+// keeps the limb-wise negation and the test over all 2 L words
+template <class F, bool RAW = false, bool SLIM = false>
 __device__ __forceinline__ void unpack_base(Fe<F> &x, Fe<F> &y, bool &inf, const PackedBase<F> &b, u32 entry)
 {
     constexpr int L = F::L;
+    constexpr bool WORDS_NEG = SLIM && acc_item<F>(ACC_ITEM_WORDS_NEG);
+    // The row is the identity iff all its 2 L words are zero.  Over the slim fields a row that is not holds a canonical point of a
+    // group of odd (prime) order, and a point with y == 0 has order two: there is none, so the L words of y alone decide it, exactly.
+    constexpr int NZ_FROM = SLIM && acc_item<F>(ACC_ITEM_Y_IDENTITY) ? L : 0;
     u32 nz = 0;
 #pragma unroll
-    for (int k = 0; k < 2 * L; k++) nz |= b.w[k];
+    for (int k = NZ_FROM; k < 2 * L; k++) nz |= b.w[k];
+    if constexpr (WORDS_NEG) asm volatile("" : "+v"(nz)); // taken here: behind the negation it would keep y's words alive beside their negatives
     inf = (nz == 0);
     fe_unpack(x, b.w);
-    fe_unpack(y, b.w + L);
-    if (entry >> 31) {
-        Fe<F> ny;
-        if constexpr (RAW)
-            fe_neg_raw<F, 1>(ny, y); // y is canonical (< p)
-        else
-            fe_neg<F, 1>(ny, y);
-        y = ny;
+    if constexpr (WORDS_NEG) {
+        // a negative digit: p - y on the packed words, L subtractions under the branch's exec mask.  y is canonical, so is the result,
+        // and it unpacks tight like any other y.  An identity row's y = 0 comes back as p: `inf` was taken from the words before, and
+        // no caller looks at the coordinates of an identity row.
+        u32 yw[L];
+#pragma unroll
+        for (int k = 0; k < L; k++) yw[k] = b.w[L + k];
+        if (entry >> 31) fe_words_neg<F>(yw, b.w + L);
+        fe_unpack(y, yw);
+    } else {
+        fe_unpack(y, b.w + L);
+        if (entry >> 31) {
+            Fe<F> ny;
+            if constexpr (RAW)
+                fe_neg_raw<F, 1>(ny, y); // y is canonical (< p)
+            else
+                fe_neg<F, 1>(ny, y);
+            y = ny;
+        }
     }
 }
 
@@ -513,18 +587,20 @@ __device__ __forceinline__ void accumulate_chunk(const u32 *__restrict__ bases, 
     const bool quads = ((reinterpret_cast<uintptr_t>(sw + start) & 15) == 0); // chunk starts are multiples of K >= 16 words; tiny lists may not be aligned
     // sectors: the chunk starts on 64 bytes (K a multiple of 16 words); sector s of the chunk sits in buffer s & 1
     const bool sectors = SWLDS && ((reinterpret_cast<uintptr_t>(sw + start) & 63) == 0);
-    auto sector_to_lds = [&](u32 sector) { // at most 60 bytes past the list's end, inside the arena
-        const u32 *src = sw + start + 16 * sector;
+    auto sector_to_lds = [&](u32 sector, const u32 *src) { // src: the sector's words, sw + start + 16 * sector; at most 60 bytes past the list's end, inside the arena
+        // the LDS address of the transfer comes from M0, one for the wave: the lanes run in lock step, so `sector` is the same in all of
+        // them -- said here, not left to be inferred
+        const u32 buffer = (u32)__builtin_amdgcn_readfirstlane((int)(sector & 1u));
 #pragma unroll
         for (int q = 0; q < 4; q++)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + 4 * q),
-                                             (__attribute__((address_space(3))) void *)(lds_words + (sector & 1u) * 256 + q * 64), 16, 0, 0);
+                                             (__attribute__((address_space(3))) void *)(lds_words + buffer * 256 + q * 64), 16, 0, 0);
     };
     uint4 quad = make_uint4(0, 0, 0, 0);
     if constexpr (SWLDS) {
         if (sectors) {
-            sector_to_lds(0);
-            if (start + 16 < end) sector_to_lds(1);
+            sector_to_lds(0, sw + start);
+            if (start + 16 < end) sector_to_lds(1, sw + start + 16);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // nothing else is in flight yet
             quad = lds_words[lane];
         } else if (quads)
@@ -533,79 +609,164 @@ __device__ __forceinline__ void accumulate_chunk(const u32 *__restrict__ bases, 
         quad = *reinterpret_cast<const uint4 *>(sw + start); // at most 12 bytes past the list's end, inside the arena
     u32 cur_entry = quads ? quad.x : sw[start];
     u32 ahead_entry = quads ? quad.y : (start + 1 < end ? sw[start + 1] : 0u);
+    constexpr bool ROW_TUPLES = !LDSROW && acc_item<F>(ACC_ITEM_ROW_TUPLES);
+    constexpr int ROW_LOADS = 2 * F::L / 4; // vector memory operations of one row gather
+    PackedRow<F> next_row;
     if constexpr (LDSROW)
         fetch_base_lds<F>(lds_wave, bases, cur_entry);
+    else if constexpr (ROW_TUPLES)
+        fetch_row<F>(next_row, bases, cur_entry);
     else
         fetch_base<F>(next_base, bases, cur_entry);
-    for (u32 pos = start; pos < end; pos++) {
+    constexpr bool QUAD_SHIFT = acc_item<F>(ACC_ITEM_QUAD_SHIFT);
+    constexpr bool ID_FLAG = acc_item<F>(ACC_ITEM_ID_FLAG);
+    constexpr bool SLIM_BOUNDARY = ID_FLAG && acc_item<F>(ACC_ITEM_BOUNDARY);
+    // a y that may be stored as it comes out of unpack_base: tight (never negated limb-wise) or loose (fe_neg), not raw
+    constexpr bool Y_STORABLE = acc_item<F>(ACC_ITEM_WORDS_NEG) || !(ACC_RAW_Y && RawOperandOk<F>::value);
+    // ID_FLAG: the accumulator is the identity (and its registers hold the identity's zeros).  It can only become the identity where
+    // this loop makes it so -- at the chunk's start, at a boundary, after P + (-P) -- or by doubling a point of order two.
+    bool acc_id = true;
+    u32 *brun = bw + (u64)b * PW; // SLIM_BOUNDARY: bucket b's accumulator, moved along with b
+    if constexpr (QUAD_SHIFT) { // the quad's words come out of .x, one per trip: words 0 and 1 are taken, the next shift brings up word 2
+        quad.x = quad.y;
+        quad.y = quad.z;
+        quad.z = quad.w;
+    }
+    // trip == pos - start, kept apart so that the compiler sees it is the same in every lane of the wave
+    u32 trip = 0;
+    for (u32 pos = start; pos < end; pos++, trip++) {
         Fe<F> cx, cy;
         bool cinf;
         const u32 entry = cur_entry;
         if constexpr (LDSROW) read_base_lds<F>(next_base, lds_wave, lane);
-        unpack_base<F, ACC_RAW_Y && RawOperandOk<F>::value>(cx, cy, cinf, next_base, entry);
+        if constexpr (ROW_TUPLES) row_words<F>(next_base, next_row); // the wait for the row is here, at its first use
+        unpack_base<F, ACC_RAW_Y && RawOperandOk<F>::value, true>(cx, cy, cinf, next_base, entry);
+        if constexpr (ROW_TUPLES) {
+            // the row is unpacked HERE, before the next gather is issued into the registers it sits in: left free, the compiler moves the
+            // unpacking of x down to the addition, keeps x's eight words alive across the gather, and copies them out of its way
+#pragma unroll
+            for (int i = 0; i < F::N; i++) asm volatile("" : "+v"(cx.l[i]), "+v"(cy.l[i]));
+        }
         const bool boundary = pos >= next;
         if (boundary) { // the run of bucket b ends here; this entry opens the next run, so it simply becomes the accumulator
-            store_xyzz<F>(run_starts_inside ? bw + (u64)b * PW : pw, acc); // its end (== pos) is inside the chunk by construction
-            run_starts_inside = true;
-            do {
-                b++;
-                next = ow[b + 1];
-            } while (next <= pos);
-            if (cinf)
-                xyzz_set_identity(acc);
-            else {
-                Fe<F> ty;
-                fe_norm(ty, cy);
-                xyzz_from_affine(acc, cx, ty);
+            if constexpr (SLIM_BOUNDARY) {
+                store_xyzz<F>(run_starts_inside ? brun : pw, acc); // its end (== pos) is inside the chunk by construction
+                run_starts_inside = true;
+                do {
+                    b++;
+                    brun += PW;
+                    next = ow[b + 1];
+                } while (next <= pos);
+                // the new run starts from the identity; the opening row then becomes the accumulator below, where every row that meets
+                // an identity accumulator does (one copy of that code, behind the gather's issue)
+                if (cinf) xyzz_set_identity(acc);
+                acc_id = true;
+            } else {
+                store_xyzz<F>(run_starts_inside ? bw + (u64)b * PW : pw, acc); // its end (== pos) is inside the chunk by construction
+                run_starts_inside = true;
+                do {
+                    b++;
+                    next = ow[b + 1];
+                } while (next <= pos);
+                acc_id = cinf;
+                if (cinf)
+                    xyzz_set_identity(acc);
+                else {
+                    Fe<F> ty;
+                    fe_norm(ty, cy);
+                    xyzz_from_affine(acc, cx, ty);
+                }
             }
         }
         if (pos + 1 < end) {
             cur_entry = ahead_entry;
             if constexpr (LDSROW)
                 fetch_base_lds<F>(lds_wave, bases, cur_entry);
+            else if constexpr (ROW_TUPLES)
+                fetch_row<F>(next_row, bases, cur_entry);
             else
                 fetch_base<F>(next_base, bases, cur_entry);
             if (pos + 2 < end) {
                 if (quads) {
-                    const u32 idx = pos + 2 - start;
+                    const u32 idx = QUAD_SHIFT ? trip + 2 : pos + 2 - start;
                     if ((idx & 3u) == 0) {
                         if (SWLDS && sectors) {
-                            // the sector was sent to LDS sixteen entries ago (or at the start), i.e. before the row gather that the top of this
-                            // iteration waited for: the counter is in order, so it has landed.  Entering sector s frees the other buffer (sector
-                            // s - 1 has been read to its end) for sector s + 1.
-                            if ((idx & 15u) == 0 && start + idx + 16 < end) sector_to_lds((idx >> 4) + 1);
+                            // Entering sector s frees the other buffer (sector s - 1 has been read to its end) for sector s + 1.  Sector s itself
+                            // was sent to LDS sixteen entries ago (or at the start, and waited for there).  The counter of vector memory operations
+                            // is in order, and the only ones younger than that transfer which may still be out are this trip's row gather and the
+                            // transfer of sector s + 1 just issued: waiting until no more than those are outstanding says sector s has landed.
+                            // (Where only some lanes have a sector s + 1 both waits run, and the stricter one holds.)
+                            if ((idx & 15u) == 0) {
+                                if (pos + 18 < end) { // start + idx == pos + 2: the loop needs neither `start` nor a pointer to the chunk
+                                    sector_to_lds((idx >> 4) + 1, sw + pos + 18);
+                                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ROW_LOADS + 4) : "memory");
+                                } else
+                                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ROW_LOADS) : "memory");
+                            }
                             quad = lds_words[((idx >> 4) & 1u) * 256 + ((idx >> 2) & 3u) * 64 + lane];
-                        } else
+                        } else {
                             quad = *reinterpret_cast<const uint4 *>(sw + pos + 2);
+                            // (tiny, unaligned lists) the quad is waited for here, where it is loaded: left to its first use, the wait would
+                            // sit in front of the shift of every trip -- and take the row gather issued just above with it
+                            if constexpr (ROW_TUPLES) asm volatile("" : "+v"(quad.x), "+v"(quad.y), "+v"(quad.z), "+v"(quad.w));
+                        }
+                    } else if constexpr (QUAD_SHIFT) {
+                        quad.x = quad.y;
+                        quad.y = quad.z;
+                        quad.z = quad.w;
                     }
-                    ahead_entry = (idx & 2u) ? ((idx & 1u) ? quad.w : quad.z) : ((idx & 1u) ? quad.y : quad.x);
-                } else
+                    if constexpr (QUAD_SHIFT)
+                        ahead_entry = quad.x;
+                    else
+                        ahead_entry = (idx & 2u) ? ((idx & 1u) ? quad.w : quad.z) : ((idx & 1u) ? quad.y : quad.x);
+                } else {
                     ahead_entry = sw[pos + 2];
+                    if constexpr (ROW_TUPLES) asm volatile("" : "+v"(ahead_entry)); // waited for here, as the quad of the tiny lists above
+                }
             }
         }
-        if (boundary) continue;
+        if constexpr (!SLIM_BOUNDARY)
+            if (boundary) continue;
         if (cinf) continue;
-        if (xyzz_is_identity(acc)) {
-            Fe<F> ty;
-            fe_norm(ty, cy); // a raw negated y must not be stored
-            xyzz_from_affine(acc, cx, ty);
+        if (ID_FLAG ? acc_id : xyzz_is_identity(acc)) {
+            if constexpr (SLIM_BOUNDARY && Y_STORABLE) {
+                // the row becomes the accumulator by eighteen moves spelled out: as plain copies the compiler leaves x and y where they
+                // were unpacked -- untouched through the whole addition the other lanes run -- and moves them at the end of the trip
+#pragma unroll
+                for (int i = 0; i < F::N; i++) {
+                    asm("v_mov_b32 %0, %1" : "=v"(acc.X.l[i]) : "v"(cx.l[i]));
+                    asm("v_mov_b32 %0, %1" : "=v"(acc.Y.l[i]) : "v"(cy.l[i]));
+                }
+                fe_one(acc.ZZ);
+                fe_one(acc.ZZZ);
+            } else {
+                Fe<F> ty;
+                fe_norm(ty, cy); // a raw negated y must not be stored
+                xyzz_from_affine(acc, cx, ty);
+            }
+            acc_id = false;
             continue;
         }
         const int rare = xyzz_madd_core(acc, cx, cy);
         if (rare) { // same x as the accumulator: reload the base instead of keeping it live through the common path
             if (rare == 1) {
                 PackedBase<F> again;
-                fetch_base<F>(again, bases, entry);
-                unpack_base<F>(cx, cy, cinf, again, entry);
+                // (the slim loop does not keep the sorted word through the addition either: one register)
+                const u32 same = acc_item<F>(ACC_ITEM_WORDS_NEG) ? sw[pos] : entry;
+                fetch_base<F>(again, bases, same);
+                unpack_base<F, false, true>(cx, cy, cinf, again, same);
                 xyzz_dbl_affine(acc, cx, cy);
-            } else
+                acc_id = xyzz_is_identity(acc);
+            } else {
                 xyzz_set_identity(acc);
+                acc_id = true;
+            }
         }
     }
     // last run: complete only if the bucket both starts and ends inside the chunk
     const bool starts_inside = run_starts_inside;
     const bool ends_inside = next <= end;
-    u32 *dst = (starts_inside && ends_inside) ? bw + (u64)b * PW : (starts_inside ? pw + PW : pw);
+    u32 *dst = (starts_inside && ends_inside) ? (SLIM_BOUNDARY ? brun : bw + (u64)b * PW) : (starts_inside ? pw + PW : pw);
     store_xyzz<F>(dst, acc);
 }
 
