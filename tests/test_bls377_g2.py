@@ -14,6 +14,7 @@ import pytest
 import oracle as po
 import pyref
 import pyref_bls377_g2 as g2
+from gpu_util import gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 from panda_amd import multi_gpu
@@ -304,13 +305,6 @@ def _device_bases(seed, n, first=0):
     bases = db.to_host().reshape(n, 48)
     db.free()
     return bases
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
 
 
 @pytest.mark.gpu

@@ -8,21 +8,18 @@ Every device buffer carries a guard run of a fixed byte pattern behind the data,
 call must come back unchanged.  The host program tests/host_check/ec_ntt_host.cpp runs the per-thread routines under FE29_CHECK."""
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
 import pyref
+from gpu_util import GuardedBuffers, assert_exported, gm, run_host_check  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-GUARD, GUARD_BYTES = 0xA5, 4096
 NAMES = ("panda_ec_ntt", "panda_ec_ntt_plan", "panda_points_to_affine", "panda_points_to_affine_plan")
 CURVES = (0, 1, 2)
 FORWARD, INVERSE = 0, 1
@@ -62,12 +59,6 @@ def _mul_g(curve, k):
     return pyref.ec_mul(c, k % c.r, c.g)
 
 
-def _scalars(curve, seed, n):
-    r = pyref.CURVES[curve].r
-    raw = np.random.default_rng(seed).bytes(40 * n)
-    return [int.from_bytes(raw[40 * j:40 * j + 40], "little") % r for j in range(n)]
-
-
 def _dft(curve, s, log_n, inverse=False, ks=None):
     """sum_j s_j w^(jk) mod r for k in ks (all k by default); w = omega, or omega^-1 with the 1 / n"""
     c, n = pyref.CURVES[curve], 1 << log_n
@@ -89,14 +80,7 @@ def _plan(lib, curve, log_n, direction):
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in NAMES:
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    header, _ = assert_exported(NAMES)
     assert len(set(NAMES)) == 4 and "panda_ec_ntt_gpu" in dir(pgm) and "panda_points_gpu_to_affine" in dir(pgm)
     for macro, value in (("PANDA_EC_NTT_FORWARD", "0u"), ("PANDA_EC_NTT_INVERSE", "1u"), ("PANDA_EC_NTT_MAX_LOG_N", "26")):
         assert re.search(r"#define\s+%s\s+%s\b" % (macro, value), header)
@@ -150,7 +134,7 @@ def _refusals(lib, curve, IN, OUT, log_n, stream, untouched):
     assert call(d_in=None) == 1 and call(d_out=None) == 1 and call(omega=None) == 1 and call(omega=None, log_n=0) == 1
     assert call(omega=pyref.int_to_limbs(c.r, 8)) == 1 and call(omega=np.full(8, 0xFFFFFFFF, np.uint32)) == 1, "omega >= the modulus"
     w = _omega(curve, log_n)
-    to_wire = lambda v: pyref.int_to_limbs(v % c.r * c.Rr % c.r, 8)
+    to_wire = lambda v: fr.wire_one(curve, v)
     assert call(omega=to_wire(w * w)) == 1, "omega^2: a root of half the order"
     assert call(omega=_omega_wire(curve, log_n + 1)) == 1, "the root of the next size up"
     assert call(omega=to_wire(1)) == 1 and call(omega=to_wire(0)) == 1 and call(omega=to_wire(c.r - 1)) == (0 if log_n == 1 else 1)
@@ -175,56 +159,20 @@ def test_host_program_checks_the_bounds_and_the_exceptional_cases(tmp_path):
     under FE29_CHECK against the affine law in integer arithmetic of its own, for the three curves: B, A and both the identity,
     w B = A, w B = -A, the twiddles 1, r - 1 and one with the top bit set, a chunk of identities only and one whose first and last
     points are identities; every stored point is checked against the stored-point bounds"""
-    exe = str(tmp_path / "ec_ntt_host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-o", exe, os.path.join(HERE, "host_check", "ec_ntt_host.cpp")], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert re.fullmatch(r"ok (\d+)\n", out.stdout) and int(out.stdout.split()[1]) >= 5000
+    assert run_host_check(tmp_path, "ec_ntt_host.cpp") >= 5000
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
-class Dev:
-    """device buffers with a guard run behind the data, and the transform over them"""
+class Dev(GuardedBuffers):
+    """guarded device buffers, and the transform over them"""
 
     def __init__(self, gm, curve=0):
-        self.lib, self.curve, self.stream, self.bufs = ffi.load(), curve, gm.exec_stream.raw, []
-
-    def buffer(self, x=None, nbytes=None):
-        from gpu_util import DeviceBuffer
-        if x is not None:
-            x = np.ascontiguousarray(x, np.uint32)
-            nbytes = x.nbytes
-        d = DeviceBuffer(nbytes + GUARD_BYTES)
-        d.data_bytes, d.host = nbytes, x
-        self.bufs.append(d)
-        ffi.check(self.lib.panda_memset(d.ptr, GUARD, nbytes + GUARD_BYTES), "memset")
-        if x is not None and nbytes:
-            ffi.check(self.lib.panda_memcpy(d.ptr, C.c_void_p(x.ctypes.data), nbytes), "memcpy")
-        return d
-
-    def get(self, d):
-        return d.to_host(np.uint32, nbytes=d.data_bytes)
-
-    def intact(self, d):
-        """the guard behind the data, and the data itself if the buffer was an input"""
-        guard = (d.to_host(np.uint8, nbytes=GUARD_BYTES, offset=d.data_bytes) == GUARD).all()
-        return bool(guard and (d.host is None or np.array_equal(self.get(d), d.host.reshape(-1))))
+        super().__init__()
+        self.lib, self.curve, self.stream = ffi.load(), curve, gm.exec_stream.raw
 
     def ntt(self, src, dst, log_n, direction=FORWARD, omega=None):
         om = np.ascontiguousarray(_omega_wire(self.curve, log_n) if omega is None else omega)
         return self.lib.panda_ec_ntt(self.curve, src.ptr, dst.ptr, log_n, direction, C.c_void_p(om.ctypes.data), self.stream)
-
-    def close(self):
-        for d in self.bufs:
-            d.free()
-        self.bufs = []
 
 
 def _transform(gm, curve, words, log_n, direction=FORWARD, what=""):
@@ -250,7 +198,7 @@ def test_definition(gm, curve):
     """log_n = 0 .. 4, both directions: P_j = s_j G, out[k] = (sum_j s_j omega^(jk)) G, the whole output byte for byte"""
     for log_n in range(5):
         n = 1 << log_n
-        s = _scalars(curve, 0xEC00 + 16 * curve + log_n, n)
+        s = fr.random_residues(curve, 0xEC00 + 16 * curve + log_n, n)
         words = _enc_all(curve, [_mul_g(curve, v) for v in s])
         for direction in (FORWARD, INVERSE):
             want = _enc_all(curve, [_mul_g(curve, v) for v in _dft(curve, s, log_n, direction == INVERSE)])
@@ -265,7 +213,7 @@ def test_log_n_zero_identity_and_random_half_identities(gm):
         c = pyref.CURVES[curve]
         ident = np.concatenate([np.zeros(c.lc_q, np.uint32), pyref.int_to_limbs(c.Rq, c.lc_q)])[None, :]
         assert not _transform(gm, curve, ident, 0).any() and not _transform(gm, curve, ident, 0, INVERSE).any()
-        s = _scalars(curve, 0xEC80 + curve, 16)
+        s = fr.random_residues(curve, 0xEC80 + curve, 16)
         hole = np.random.default_rng(0xEC90 + curve).permutation(16)[:8]
         for j in hole:
             s[j] = 0
@@ -291,7 +239,7 @@ def test_across_workgroups_and_both_stage_kinds(gm, curve):
     assert (n // 2) // 64 > 1, "more than one workgroup per stage (a workgroup is 64 butterflies)"
     assert len(SAMPLES_12) == 64 and {0, 1, n // 2, n - 1} <= set(SAMPLES_12)
     c = pyref.CURVES[curve]
-    a, d = _scalars(curve, 0xEC20 + curve, 2)
+    a, d = fr.random_residues(curve, 0xEC20 + curve, 2)
     step, P, pts = _mul_g(curve, d), _mul_g(curve, a), []
     for j in range(n):
         pts.append(P)
@@ -308,9 +256,7 @@ def test_across_workgroups_and_both_stage_kinds(gm, curve):
         assert h.ntt(mid, back, log_n, INVERSE) == 0 and h.intact(back)
         _compare(h.get(back).reshape(n, -1), words, "inverse(forward), out of place")
         assert np.array_equal(h.get(mid).reshape(n, -1), got), "the input of an out-of-place call changed"
-        assert h.ntt(mid, mid, log_n, INVERSE) == 0 and h.intact(back)
-        guard = mid.to_host(np.uint8, nbytes=GUARD_BYTES, offset=mid.data_bytes)
-        assert (guard == GUARD).all()
+        assert h.ntt(mid, mid, log_n, INVERSE) == 0 and h.intact(back) and h.guard_intact(mid)
         _compare(h.get(mid).reshape(n, -1), words, "inverse(forward), in place")
         assert h.ntt(mid, mid, log_n, FORWARD) == 0
         _compare(h.get(mid).reshape(n, -1), got, "forward in place equals forward out of place")
@@ -322,7 +268,7 @@ def test_across_workgroups_and_both_stage_kinds(gm, curve):
 def test_random_points_at_2_to_8(gm):
     """BN254, 2^8 random s_j: 16 sampled outputs against the definition and the round trip over the whole buffer"""
     curve, log_n, n = 0, 8, 256
-    s = _scalars(curve, 0xEC88, n)
+    s = fr.random_residues(curve, 0xEC88, n)
     words = _enc_all(curve, [_mul_g(curve, v) for v in s])
     got = _transform(gm, curve, words, log_n)
     ks = [0, 1, 2, 3, 64, 127, 128, 129, 200, 254, 255, 17, 33, 65, 99, 192]
@@ -338,7 +284,7 @@ def test_structured_inputs_with_closed_forms(gm, curve):
     j in {0, 1, n - 1} -> out[k] = omega^(jk) P; all identities -> all identities.  log_n = 6 whole buffer; 12 whole buffer for the
     closed forms with one non-identity output, sampled outputs for the single point"""
     c = pyref.CURVES[curve]
-    P = _mul_g(curve, _scalars(curve, 0xEC60 + curve, 1)[0])
+    P = _mul_g(curve, fr.random_residues(curve, 0xEC60 + curve, 1)[0])
     neg = (P[0], (-P[1]) % c.p)
     w6 = _omega(curve, 6)
     table = [None] * 64  # omega_6^k P
@@ -409,7 +355,7 @@ def test_refusals_leave_the_guarded_output_untouched(gm):
             room = h.buffer(_enc_all(curve, [_mul_g(curve, j + 1) for j in range(48)]))  # IN is its middle third
             out = h.buffer(nbytes=48 * pb)
             IN, OUT = room.ptr.value + 16 * pb, out.ptr.value + 16 * pb
-            untouched = lambda: h.intact(room) and bool((out.to_host(np.uint8) == GUARD).all())
+            untouched = lambda: h.intact(room) and h.untouched(out)
             assert _refusals(lib, curve, IN, OUT, log_n, h.stream, untouched) > 30
             # a buffer of the library's allocator shorter than stated
             short = DeviceBuffer(16 * pb)

@@ -9,7 +9,7 @@ import pytest
 
 import oracle as po
 import pyref
-from gpu_util import NULL_STREAM, DeviceBuffer
+from gpu_util import NULL_STREAM, DeviceBuffer, gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 from panda_amd import multi_gpu
@@ -21,14 +21,6 @@ def _soak(*values):
     """a case of an off-by-default experiment path that only runs under `-m gpu_soak` (tests/conftest.py): `-m gpu` keeps one representative
     case per path -- the fuzzers (tools/fuzz_msm.py, fuzz_ntt.py, fuzz_ranges.py) cover these paths at random"""
     return pytest.param(*values, marks=pytest.mark.gpu_soak)
-
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
 
 
 @pytest.fixture(autouse=True)

@@ -7,21 +7,18 @@ Python integers -- not the fraction (f(tau) - f(z)) / (tau - z), so tau on the d
 (tests/points_ref.py); every comparison is byte for byte, every device buffer carries a guard run, inputs must come back unchanged."""
 import ctypes as C
 import functools
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
 import pyref
+from gpu_util import assert_exported, gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
-from points_ref import CURVES, Dev, compare, enc_multiples, host_ptr, point_bytes, random_scalars, scalar_wire, scalars_wire
+from points_ref import CURVES, Dev, compare, enc_multiples, host_ptr, point_bytes
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NAMES = ("panda_kzg_open_all_setup", "panda_kzg_open_all", "panda_kzg_open_all_plan")
 gpu = pytest.mark.gpu
 
@@ -51,12 +48,7 @@ def _ptr(v):
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_and_plan():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in NAMES:
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header) and name in ffi.ADDITIVE_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M) and getattr(lib, name).argtypes is not None
+    _, lib = assert_exported(NAMES)
     assert "PandaKzgOpenAll" in dir(pgm)
     u = C.c_uint
     for curve in CURVES:
@@ -96,7 +88,7 @@ def _refusals(lib, curve, log_n, SRS, TABLE, COEFFS, WORK, PROOFS, stream, untou
         assert untouched(), "a refused open wrote to a buffer"
         return rc
 
-    to_wire = lambda v: np.ascontiguousarray(scalar_wire(curve, v))
+    to_wire = lambda v: np.ascontiguousarray(fr.wire_one(curve, v))
     w2 = pyref.decode_scalar(c, good)
     bad_roots = (np.ascontiguousarray(pyref.int_to_limbs(c.r, 8)), np.full(8, 0xFFFFFFFF, np.uint32), to_wire(w2 * w2), to_wire(1), to_wire(0),
                  _omega2_wire(curve, log_n + 1), _omega2_wire(curve, log_n - 1) if log_n > 1 else to_wire(c.r - 1))
@@ -128,13 +120,6 @@ def test_bad_arguments_are_refused_before_any_device_call():
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
 def _reference(curve, f, tau, log_n):
     """the n proofs as integers e_k with proof_k = e_k G: e_k = sum_j q_j tau^j, q the quotient of f by X - omega^k (synthetic division)"""
     r, n, w = pyref.CURVES[curve].r, 1 << log_n, _omega(curve, log_n)
@@ -160,7 +145,7 @@ def _open_all(gm, curve, log_n, f, tau, what, opens=1):
     try:
         srs = h.buffer(enc_multiples(curve, [pow(tau, i, r) for i in range(n)]))
         table, work, proofs = h.buffer(nbytes=2 * n * pb), h.buffer(nbytes=work_bytes), h.buffer(nbytes=n * pb)
-        coeffs = h.buffer(scalars_wire(curve, f))
+        coeffs = h.buffer(fr.wire(curve, f))
         assert lib.panda_kzg_open_all_setup(curve, srs.ptr, log_n, host_ptr(om), table.ptr, h.stream) == 0, what
         assert h.intact(srs) and h.guard_intact(table) and h.untouched(work) and h.untouched(proofs), (what, "setup")
         table.host = h.get(table)
@@ -187,8 +172,8 @@ def _check(gm, curve, log_n, f, tau, what, opens=1):
 def test_small_domains(gm, curve):
     """log_n = 1 .. 4, random f and tau, the whole output; two opens give the same bytes"""
     for log_n in (1, 2, 3, 4):
-        tau, = random_scalars(curve, 0xF200 + 16 * curve + log_n, 1)
-        f = random_scalars(curve, 0xF280 + 16 * curve + log_n, 1 << log_n)
+        tau, = fr.random_residues(curve, 0xF200 + 16 * curve + log_n, 1)
+        f = fr.random_residues(curve, 0xF280 + 16 * curve + log_n, 1 << log_n)
         _check(gm, curve, log_n, f, tau, (curve, log_n), opens=2)
 
 
@@ -198,8 +183,8 @@ def test_special_cases(gm, curve):
     """log_n = 3: tau = omega^3 (the SRS repeats, and the fraction's division by zero is not the reference's); tau = 1 (every SRS point is
     G: doublings and cancellations only); f constant (all identities); f with a zero top coefficient; f = X^(n - 1)"""
     log_n, n, r = 3, 8, pyref.CURVES[curve].r
-    f = random_scalars(curve, 0xF300 + curve, n)
-    tau, = random_scalars(curve, 0xF310 + curve, 1)
+    f = fr.random_residues(curve, 0xF300 + curve, n)
+    tau, = fr.random_residues(curve, 0xF310 + curve, 1)
     _check(gm, curve, log_n, f, pow(_omega(curve, log_n), 3, r), "tau on the domain")
     _check(gm, curve, log_n, f, 1, "tau = 1")
     assert not _check(gm, curve, log_n, [f[0]] + [0] * (n - 1), tau, "f constant").any()
@@ -212,8 +197,8 @@ def test_special_cases(gm, curve):
 @pytest.mark.parametrize("curve,log_n", ((0, 8), (1, 6), (2, 6)))
 def test_uniform_and_divergent_stages(gm, curve, log_n):
     """the whole output at 2n = 512 on BN254 (uniform and divergent EC-NTT stages, eight multiplication waves) and 2n = 128 on the BLS curves"""
-    tau, = random_scalars(curve, 0xF400 + curve, 1)
-    _check(gm, curve, log_n, random_scalars(curve, 0xF410 + curve, 1 << log_n), tau, (curve, log_n))
+    tau, = fr.random_residues(curve, 0xF400 + curve, 1)
+    _check(gm, curve, log_n, fr.random_residues(curve, 0xF410 + curve, 1 << log_n), tau, (curve, log_n))
 
 
 @gpu
@@ -239,7 +224,7 @@ def test_against_division_and_msm_on_the_device(gm):
     assert proofs.shape == (n, 64) and np.array_equal(proofs, again)
     w = _omega(curve, log_n)
     for k in (0, 1, 512, 1023):
-        quot, _ = pgm.panda_poly_gpu_divide(gm, [coeffs], scalar_wire(curve, pow(w, k, c.r)), curve)
+        quot, _ = pgm.panda_poly_gpu_divide(gm, [coeffs], fr.wire_one(curve, pow(w, k, c.r)), curve)
         want = pyref.decode_jacobian(c, pgm.panda_msm_bn254_gpu(gm, quot[0], srs, curve).view(np.uint32))
         assert want is not None and pyref.decode_affine(c, proofs[k].view(np.uint32)) == want, k
 
@@ -253,7 +238,7 @@ def test_refusals_leave_the_guarded_buffers_untouched(gm):
             log_n, n, pb = 3, 8, point_bytes(curve)
             rc, work_bytes, _ = _plan(lib, curve, log_n)
             srs = h.buffer(enc_multiples(curve, range(1, 3 * n + 1)))
-            coeffs = h.buffer(scalars_wire(curve, range(7, 7 + 3 * n)))
+            coeffs = h.buffer(fr.wire(curve, range(7, 7 + 3 * n)))
             table, work, proofs = h.buffer(nbytes=4 * n * pb), h.buffer(nbytes=work_bytes + 2 * n * pb), h.buffer(nbytes=3 * n * pb)
             untouched = lambda: h.intact(srs) and h.intact(coeffs) and all(h.untouched(b) for b in (table, work, proofs))
             args = (srs.ptr.value + n * pb, table.ptr.value + n * pb, coeffs.ptr.value + n * 32, work.ptr.value + n * pb, proofs.ptr.value + n * pb)

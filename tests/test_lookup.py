@@ -9,45 +9,25 @@ comparison is byte for byte.  Every boundary size of the running sum comes from 
 guard run of a fixed byte pattern behind the data, which no call may touch; inputs must come back unchanged unless they are the output."""
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
-import pyref
+from gpu_util import GUARD, GuardedBuffers, assert_exported, free_bytes, gm, run_host_check  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
 MAX_ELEMS = 1 << 28
-GUARD, GUARD_BYTES = 0xA5, 4096
-W = 1 << 256
 NONE_MISSING = (1 << 64) - 1
 NAMES = ("panda_lookup_multiplicities", "panda_lookup_plan", "panda_lookup_home_slot", "panda_poly_running_sum", "panda_poly_running_sum_plan")
 
 
-@functools.lru_cache(maxsize=None)
-def _modulus(field):
-    return pyref.limbs_to_int(po.field_info(po.FR_OF[field])["p"])
-
-
 def _wire_int(field, v):
-    r = _modulus(field)
-    return v % r * W % r
-
-
-def _words(vals):
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), np.uint32).reshape(-1, 8)
-
-
-def _ints(a):
-    raw = np.ascontiguousarray(a, np.uint32).reshape(-1, 8).tobytes()
-    return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+    r = fr.modulus(field)
+    return v % r * fr.W % r
 
 
 def _keys(a):
@@ -106,21 +86,14 @@ def _lookup_expected(field, table, cols):
 
 def _sum_expected(field, x):
     """(exclusive running sums (n, 8), total (8,)) of one vector"""
-    r = _modulus(field)
-    sums = np.add.accumulate(np.array([0] + _ints(x), dtype=object)) % r  # Python integers: the running sum, then % r
-    return _words(sums[:-1]), _words(sums[-1:])[0]
+    r = fr.modulus(field)
+    sums = np.add.accumulate(np.array([0] + fr.ints(x), dtype=object)) % r  # Python integers: the running sum, then % r
+    return fr.words(sums[:-1]), fr.words(sums[-1:])[0]
 
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in NAMES:
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    header, lib = assert_exported(NAMES)
     assert lib.panda_lookup_multiplicities.argtypes[2] is C.c_uint64 and lib.panda_lookup_multiplicities.argtypes[5] is C.c_uint64
     assert lib.panda_lookup_plan.argtypes[0] is C.c_uint64 and lib.panda_lookup_plan.argtypes[2] is C.c_uint64
     assert lib.panda_poly_running_sum.argtypes[3] is C.c_uint64 and lib.panda_poly_running_sum_plan.argtypes[0] is C.c_uint64
@@ -254,86 +227,47 @@ def test_host_program_checks_the_hash_and_the_bounds(tmp_path):
     """tests/host_check/lookup_host.cpp: lookup.h on the host under FE29_CHECK -- the hash against panda_lookup_home_slot, the count ->
     wire conversion at 0, 1, 2^28 - 1 and 2^28 and the running sum's addition chains at their bound with every operand p - 1, against
     256-bit arithmetic of its own, the three fields"""
-    exe = str(tmp_path / "lookup_host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-o", exe, os.path.join(HERE, "host_check", "lookup_host.cpp")], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert re.fullmatch(r"ok (\d+)\n", out.stdout) and int(out.stdout.split()[1]) >= 200
+    assert run_host_check(tmp_path, "lookup_host.cpp") >= 200
     elems = [np.array(e) for e in _pool()[:48]] + [np.zeros(8, np.uint32), np.full(8, 0xFFFFFFFF, np.uint32)]
     for log_slots in (1, 4, 5, 20, 29):
-        out = subprocess.run([exe, "hash", str(log_slots)] + [e.tobytes().hex() for e in elems], capture_output=True, text=True)
+        out = run_host_check(tmp_path, "lookup_host.cpp", "hash", str(log_slots), *[e.tobytes().hex() for e in elems])
         assert out.returncode == 0
         assert [int(v) for v in out.stdout.split()] == [_home_slot(e, log_slots) for e in elems], log_slots
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
-class Guarded:
-    """a device buffer that holds `data` with a guard run behind it; capacity for the largest data it will hold"""
-
-    def __init__(self, max_bytes):
-        from gpu_util import DeviceBuffer
-        self.lib, self.cap = ffi.load(), max_bytes + GUARD_BYTES
-        self.buf = DeviceBuffer(self.cap)
-        self.ptr, self.bytes, self.data = self.buf.ptr, 0, None
-
-    def put(self, data, nbytes=None):
-        """fill with the guard byte, then the data (None: `nbytes` of guard bytes stand where an output will go)"""
-        ffi.check(self.lib.panda_memset(self.ptr, GUARD, self.cap), "memset")
-        self.data = None if data is None else np.ascontiguousarray(data, np.uint32)
-        self.bytes = nbytes if data is None else self.data.nbytes
-        assert self.bytes + GUARD_BYTES <= self.cap
-        if data is not None:
-            ffi.check(self.lib.panda_memcpy(self.ptr, C.c_void_p(self.data.ctypes.data), self.bytes), "memcpy")
-        return self
-
-    def get(self):
-        return self.buf.to_host(np.uint32, nbytes=self.bytes).reshape(-1, 8)
-
-    def guard_ok(self):
-        return (self.buf.to_host(np.uint8, nbytes=GUARD_BYTES, offset=self.bytes) == GUARD).all()
-
-    def unchanged(self):
-        return self.guard_ok() and (np.array_equal(self.get(), self.data.reshape(-1, 8)) if self.data is not None
-                                    else (self.buf.to_host(np.uint8, nbytes=self.bytes) == GUARD).all())
-
-    def free(self):
-        self.buf.free()
-
-
-class Lookup:
-    """device buffers for a table, up to `max_columns` columns and the multiplicities"""
+class Lookup(GuardedBuffers):
+    """guarded device buffers for a table, up to `max_columns` columns and the multiplicities, with room for the largest data they will
+    hold: the guard run stands right behind the data of each run"""
 
     def __init__(self, gm, field, max_table, max_n, max_columns):
+        super().__init__()
         self.lib, self.field, self.stream = ffi.load(), field, gm.exec_stream.raw
-        self.t, self.m = Guarded(max_table * 32), Guarded(max_table * 32)
-        self.c = [Guarded(max_n * 32) for _ in range(max_columns)]
+        self.t, self.m = self.buffer(nbytes=max_table * 32), self.buffer(nbytes=max_table * 32)
+        self.c = [self.buffer(nbytes=max_n * 32) for _ in range(max_columns)]
+
+    def stage(self, table, cols):
+        self.fill(self.t, table)
+        self.fill(self.m, nbytes=len(table) * 32)
+        for d, col in zip(self.c, cols):
+            self.fill(d, col)
 
     def run(self, table, cols, pointers=None, keep=False):
         """one panda_lookup_multiplicities -> (mult (n_table, 8), missing, first_missing); checks the guards and that the inputs are
         unchanged.  pointers: for every column "t" (d_table's pointer) or the index of the staged column to pass; keep: do not restage"""
         if not keep:
-            self.t.put(table)
-            self.m.put(None, len(table) * 32)
-            for d, col in zip(self.c, cols):
-                d.put(col)
+            self.stage(table, cols)
         n = len(cols[0])
         where = list(range(len(cols))) if pointers is None else pointers
         ptrs = (C.c_void_p * len(where))(*[self.t.ptr.value if w == "t" else self.c[w].ptr.value for w in where])
         missing, first = C.c_uint64(0x1111), C.c_uint64(0x2222)
         ffi.check(self.lib.panda_lookup_multiplicities(self.field, self.t.ptr, len(table), ptrs, len(where), n, self.m.ptr, C.byref(missing), C.byref(first), self.stream),
                   "multiplicities")
-        assert self.t.unchanged(), "the table or the bytes behind it were written"
+        assert self.intact(self.t), "the table or the bytes behind it were written"
         for d, _ in zip(self.c, cols):
-            assert d.unchanged(), "a column or the bytes behind it were written"
-        assert self.m.guard_ok(), "bytes behind d_mult were written"
-        return self.m.get(), missing.value, first.value
+            assert self.intact(d), "a column or the bytes behind it were written"
+        assert self.guard_intact(self.m), "bytes behind d_mult were written"
+        return self.get(self.m).reshape(-1, 8), missing.value, first.value
 
     def check(self, table, cols, pointers=None):
         mult, missing, first = self.run(table, cols, pointers)
@@ -343,16 +277,10 @@ class Lookup:
         assert (missing, first) == (want_missing, want_first)
         return mult, missing, first
 
-    def close(self):
-        for d in [self.t, self.m] + self.c:
-            d.free()
-
 
 def _count_sum(field, mult):
     """sum of the multiplicities as an integer (each is c W mod r with a small c)"""
-    r = _modulus(field)
-    winv = pow(W, -1, r)
-    return sum(v * winv % r for v in _ints(mult))
+    return sum(fr.plain(field, mult))
 
 
 TABLE_SIZES = (1, 2, 3, 7, 8, 9, 255, 256, 257, 1000)
@@ -425,14 +353,14 @@ def test_duplicate_table_rows(gm):
     try:
         mult, missing, _ = h.check(table, [col])
         zero = np.zeros(8, np.uint32)
-        assert missing == 0 and np.array_equal(mult[2], _words([_wire_int(0, 5)])[0]) and np.array_equal(mult[5], zero) and np.array_equal(mult[6], zero)
+        assert missing == 0 and np.array_equal(mult[2], fr.words([_wire_int(0, 5)])[0]) and np.array_equal(mult[5], zero) and np.array_equal(mult[6], zero)
         for _ in range(5):
             again, _, _ = h.run(table, [col], keep=True)
             assert again.tobytes() == mult.tobytes(), "d_mult differs between two runs on the same buffers"
         same = np.broadcast_to(pool[9], (8, 8))
         col = np.concatenate([same[:3], pool[10:11]])
         mult, missing, first = h.check(same, [col])
-        assert np.array_equal(mult[0], _words([_wire_int(0, 3)])[0]) and not mult[1:].any() and missing == 1 and first == 3
+        assert np.array_equal(mult[0], fr.words([_wire_int(0, 3)])[0]) and not mult[1:].any() and missing == 1 and first == 3
         for _ in range(5):
             again, _, _ = h.run(same, [col], keep=True)
             assert again.tobytes() == mult.tobytes()
@@ -470,7 +398,7 @@ def test_misses(gm):
         with_zero = np.array(table)
         with_zero[17] = 0
         mult, missing, first = h.check(with_zero, cols)  # what held table[17] before is missing now; the zero is found once
-        assert np.array_equal(mult[17], _words([_wire_int(0, 1)])[0]) and missing >= 4
+        assert np.array_equal(mult[17], fr.words([_wire_int(0, 1)])[0]) and missing >= 4
     finally:
         h.close()
 
@@ -484,7 +412,7 @@ def test_skewed_columns(gm):
     h = Lookup(gm, 0, 1000, n, 1)
     try:
         mult, missing, _ = h.check(table, [np.broadcast_to(table[37], (n, 8))])
-        assert missing == 0 and np.array_equal(mult[37], _words([_wire_int(0, n)])[0]) and _count_sum(0, mult) == n
+        assert missing == 0 and np.array_equal(mult[37], fr.words([_wire_int(0, n)])[0]) and _count_sum(0, mult) == n
         idx = np.where(rng.random(n) < 0.9, 501, rng.integers(0, 1000, n))
         mult, missing, _ = h.check(table, [table[idx]])
         assert missing == 0 and _count_sum(0, mult) == n
@@ -510,8 +438,8 @@ def test_aliased_columns(gm):
         assert all(mult[j].any() for j in first_rows) and not mult[100].any(), "every value's first row counts at least itself"
         single, _, _ = h.check(table, [col])
         double, missing, _ = h.check(table, [col], pointers=[0, 0])
-        r = _modulus(0)
-        assert missing == 0 and [v for v in _ints(double)] == [2 * v % r for v in _ints(single)]
+        r = fr.modulus(0)
+        assert missing == 0 and [v for v in fr.ints(double)] == [2 * v % r for v in fr.ints(single)]
         mixed, missing, _ = h.check(table, [col], pointers=[0, "t", 0])
         assert missing == 0 and _count_sum(0, mixed) == 3 * 513
     finally:
@@ -563,7 +491,7 @@ def test_short_buffers_are_refused(gm):
     h = Lookup(gm, 0, 64, 128, 1)
     short = DeviceBuffer(64 * 32 - 32)  # one element short of a table
     try:
-        h.t.put(table), h.m.put(None, 64 * 32), h.c[0].put(col)
+        h.stage(table, [col])
         ffi.check(h.lib.panda_memset(short.ptr, GUARD, short.nbytes), "memset")
         sentinel = 0x1234567890ABCDEF
         missing, first = C.c_uint64(sentinel), C.c_uint64(sentinel)
@@ -576,7 +504,7 @@ def test_short_buffers_are_refused(gm):
             assert rs(h.c[0].ptr, C.c_void_p(h.c[0].ptr.value + k)) == 1 and rs(C.c_void_p(h.c[0].ptr.value + k), h.c[0].ptr) == 1
             assert call(h.t.ptr, h.c[0].ptr, 128, C.c_void_p(h.t.ptr.value + k)) == 1
         assert missing.value == sentinel and first.value == sentinel and (tot == 0x77777777).all()
-        assert (short.to_host(np.uint8) == GUARD).all() and h.t.unchanged() and h.c[0].unchanged() and h.m.unchanged(), "a refused call wrote to a buffer"
+        assert (short.to_host(np.uint8) == GUARD).all() and h.intact(h.t) and h.intact(h.c[0]) and h.untouched(h.m), "a refused call wrote to a buffer"
         h.check(table, [col])
     finally:
         short.free()
@@ -584,32 +512,30 @@ def test_short_buffers_are_refused(gm):
 
 
 # ------------------------------------------------------------------------------------------------- the running sum
-class Sums:
-    """two device buffers of batch x n elements, each with a guard run behind the data"""
+class Sums(GuardedBuffers):
+    """two guarded device buffers of batch x n elements"""
 
     def __init__(self, gm, field, n, batch):
+        super().__init__()
         self.lib, self.field, self.n, self.batch, self.stream = ffi.load(), field, n, batch, gm.exec_stream.raw
-        self.a, self.o = Guarded(batch * n * 32), Guarded(batch * n * 32)
+        self.a, self.o = self.buffer(nbytes=batch * n * 32), self.buffer(nbytes=batch * n * 32)
 
     def run(self, x, where="o", totals=True):
         """one panda_poly_running_sum -> (out (batch, n, 8) or None, totals (batch, 8) or None); where: "o" out of place, "a" in place,
         None totals only (d_out == NULL)"""
-        self.a.put(x)
-        self.o.put(None, self.batch * self.n * 32)
+        self.fill(self.a, x)
+        self.fill(self.o)
+        assert self.a.data_bytes == self.o.data_bytes
         dst = {"o": self.o, "a": self.a, None: None}[where]
         tot = np.full((self.batch, 8), 0x77777777, np.uint32) if totals else None
         ffi.check(self.lib.panda_poly_running_sum(self.field, self.a.ptr, None if dst is None else dst.ptr, self.n, self.batch,
                                                   C.c_void_p(tot.ctypes.data) if totals else None, self.stream), "running_sum")
-        assert self.a.guard_ok() and self.o.guard_ok(), "bytes behind the batch were written"
+        assert self.guard_intact(self.a) and self.guard_intact(self.o), "bytes behind the batch were written"
         if where != "a":
-            assert self.a.unchanged(), "d_in was written"
+            assert self.intact(self.a), "d_in was written"
         if where != "o":
-            assert self.o.unchanged(), "a buffer that is not the output was written"
-        return (None if dst is None else dst.get().reshape(self.batch, self.n, 8)), tot
-
-    def close(self):
-        self.a.free()
-        self.o.free()
+            assert self.untouched(self.o), "a buffer that is not the output was written"
+        return (None if dst is None else self.get(dst).reshape(self.batch, self.n, 8)), tot
 
 
 @functools.lru_cache(maxsize=None)
@@ -664,8 +590,8 @@ def test_running_sum_at_the_second_level(gm, batch):
 @pytest.mark.parametrize("case", ["minus_ones", "zeros"])
 def test_running_sum_edge_values(gm, case):
     tile = _shape()[0]
-    n, batch, r = 2 * tile + 1, 2, _modulus(0)
-    v = _words([r - 1])[0] if case == "minus_ones" else np.zeros(8, np.uint32)
+    n, batch, r = 2 * tile + 1, 2, fr.modulus(0)
+    v = fr.words([r - 1])[0] if case == "minus_ones" else np.zeros(8, np.uint32)
     x = np.ascontiguousarray(np.broadcast_to(v, (batch, n, 8)))
     _check_all_forms(gm, 0, x)
     if case == "zeros":
@@ -682,14 +608,8 @@ def test_running_sum_edge_values(gm, case):
 def test_running_sum_in_the_other_fields(gm, field):
     tile = _shape()[0]
     _check_all_forms(gm, field, _vectors(field, tile + 1, 2, 0xC000 + field))
-    r = _modulus(field)
-    _check_all_forms(gm, field, np.ascontiguousarray(np.broadcast_to(_words([r - 1])[0], (1, 2 * tile + 1, 8))))
-
-
-def _free_bytes(lib):
-    free, total = C.c_size_t(0), C.c_size_t(0)
-    ffi.check(lib.panda_mem_get_info(C.byref(free), C.byref(total)), "mem_info")
-    return free.value
+    r = fr.modulus(field)
+    _check_all_forms(gm, field, np.ascontiguousarray(np.broadcast_to(fr.words([r - 1])[0], (1, 2 * tile + 1, 8))))
 
 
 @pytest.mark.gpu
@@ -705,18 +625,18 @@ def test_scratch_is_reused_and_released(gm):
         s.run(x)
         s.run(x, where=None)
         ffi.check(h.lib.panda_ntt_tear_down(), "tear_down")
-        before = _free_bytes(h.lib)
+        before = free_bytes(h.lib)
         m1 = h.run(table, cols)
-        first = _free_bytes(h.lib)
+        first = free_bytes(h.lib)
         m2 = h.run(table, cols)
-        assert _free_bytes(h.lib) == first, "a repeated identical call allocated"
+        assert free_bytes(h.lib) == first, "a repeated identical call allocated"
         o1, t1 = s.run(x)  # needs less scratch than the lookup's slots
         o2, t2 = s.run(x)
         s.run(x, where=None)
-        assert _free_bytes(h.lib) == first
+        assert free_bytes(h.lib) == first
         assert m1[0].tobytes() == m2[0].tobytes() and m1[1:] == m2[1:] and np.array_equal(o1, o2) and np.array_equal(t1, t2)
         ffi.check(h.lib.panda_ntt_tear_down(), "tear_down")
-        assert _free_bytes(h.lib) == before, "panda_ntt_tear_down releases the scratch"
+        assert free_bytes(h.lib) == before, "panda_ntt_tear_down releases the scratch"
     finally:
         h.close()
         s.close()
@@ -728,7 +648,7 @@ class _Expression:
 
     def __init__(self, ptrs, terms):
         self.ptrs = (C.c_void_p * len(ptrs))(*ptrs)
-        self.coeffs = np.ascontiguousarray(_words([k for k, _ in terms]))
+        self.coeffs = np.ascontiguousarray(fr.words([k for k, _ in terms]))
         self.degrees = (C.c_uint * len(terms))(*[len(fs) for _, fs in terms])
         flat = [f for _, fs in terms for f in fs]
         self.factors = (ffi.SopFactor * max(len(flat), 1))(*[ffi.SopFactor(c, rot) for c, rot in flat])
@@ -742,17 +662,17 @@ def test_a_real_lookup(gm):
     columns of the table's length, so h_i = sum_{k < 8} 1 / (alpha + f_k,i) - m_i / (alpha + t_i) lives on the table's domain."""
     from gpu_util import DeviceBuffer
     lib, field, stream = ffi.load(), 0, gm.exec_stream.raw
-    r = _modulus(field)
+    r = fr.modulus(field)
     nt, n, parts = 1 << 10, 1 << 12, 8
     data = po.gen_scalars(po.FR_OF[field], 0xE1, nt + 2).reshape(-1, 8)
-    table, absent, alpha_w = data[:nt], data[nt], _ints(data[nt + 1])[0]
+    table, absent, alpha_w = data[:nt], data[nt], fr.ints(data[nt + 1])[0]
     rng = np.random.default_rng(0xE1)
     witness = np.ascontiguousarray(table[rng.integers(0, nt, 2 * n)])  # the two columns end to end: eight parts of nt
-    winv = pow(W, -1, r)
+    winv = pow(fr.W, -1, r)
     # X = [f (8 x nt) | t (nt)], D = alpha + X and then 1 / D, M = multiplicities, H = h, Z = the running sum
     X, D, M, H, Z = (DeviceBuffer(k * nt * 32) for k in (parts + 1, parts + 1, 1, 1, 1))
     at = lambda d, k: d.ptr.value + k * nt * 32
-    one_w, minus_one_w = W % r, (r - 1) * W % r
+    one_w, minus_one_w = fr.W % r, (r - 1) * fr.W % r
     denominators = _Expression([X.ptr.value], [(one_w, [(0, 0)]), (alpha_w, [])])
     h_expr = _Expression([at(D, k) for k in range(parts + 1)] + [M.ptr.value],
                          [(one_w, [(k, 0)]) for k in range(parts)] + [(minus_one_w, [(parts, 0), (parts + 1, 0)])])
@@ -777,17 +697,17 @@ def test_a_real_lookup(gm):
         assert not tot.any(), "the logUp sum of a valid lookup is zero"
         # the same h and Z from Python integers, on plain values
         alpha = alpha_w * winv % r
-        f = [v * winv % r for v in _ints(witness)]
-        t = [v * winv % r for v in _ints(table)]
-        counts = [v * winv % r for v in _ints(want_m)]
+        f = [v * winv % r for v in fr.ints(witness)]
+        t = [v * winv % r for v in fr.ints(table)]
+        counts = [v * winv % r for v in fr.ints(want_m)]
         hs = [(sum(pow(alpha + f[k * nt + i], -1, r) for k in range(parts)) - counts[i] * pow(alpha + t[i], -1, r)) % r for i in range(nt)]
         zs, acc = [], 0
         for v in hs:
             zs.append(acc)
             acc = (acc + v) % r
         assert acc == 0
-        assert np.array_equal(h, _words([v * W % r for v in hs])) and np.array_equal(z, _words([v * W % r for v in zs])), "every Z_i is the running sum"
-        assert (_ints(z[-1:])[0] + _ints(h[-1:])[0]) % r == 0, "Z's last step closes"
+        assert np.array_equal(h, fr.wire(field, hs)) and np.array_equal(z, fr.wire(field, zs)), "every Z_i is the running sum"
+        assert (fr.ints(z[-1:])[0] + fr.ints(h[-1:])[0]) % r == 0, "Z's last step closes"
         bad = np.array(witness)
         bad[n + 123] = absent
         missing, first, tot, _, _, _ = chain(bad)
@@ -858,7 +778,7 @@ def test_2_24(gm):
         assert counts.sum() == n - 1000
         for c in np.unique(counts):  # every row holds the wire form of its count, so sum m is the number of values found
             rows_c = mult[counts == c]
-            assert np.array_equal(rows_c, np.broadcast_to(_words([_wire_int(0, int(c))])[0], rows_c.shape)), c
+            assert np.array_equal(rows_c, np.broadcast_to(fr.words([_wire_int(0, int(c))])[0], rows_c.shape)), c
     finally:
         h.close()
     n = (1 << 24) + 3

@@ -21,7 +21,7 @@ import pytest
 
 import oracle as po
 import pyref
-from gpu_util import NULL_STREAM, DeviceBuffer
+from gpu_util import NULL_STREAM, DeviceBuffer, gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
@@ -29,13 +29,6 @@ pytestmark = pytest.mark.gpu
 
 CURVE = pyref.CURVES[0]
 SEED = 0xACC0
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
 
 
 @pytest.fixture(autouse=True)

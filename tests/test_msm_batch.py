@@ -5,22 +5,20 @@ accumulation, one reduction that emits 2^g results); without tables the members 
 linearity identity sum s_i m_i G over panda_gen_bases seeds (O(n) on the CPU); results are compared as affine points, never as raw bytes
 (Jacobian / homogeneous coordinates are representatives, and bucket order follows wave scheduling)."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
 import pyref
 import pyref_bls377_g2 as g377
 import pyref_bls381_g2 as g381
+from gpu_util import assert_exported, gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 MAX_BATCH = 1024  # PANDA_MSM_MAX_BATCH
 CURVES = (0, 1, 2, 3, 4, 6)
 # curve id -> single-call entry point, affine base bytes, result bytes, oracle curve of the scalar field's linear combination, scalar field id
@@ -42,14 +40,7 @@ def _plan(lib, curve, log_n, window_bits, batch):
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in ("panda_msm_execute_batch", "panda_msm_batch_plan"):
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    header, _ = assert_exported(("panda_msm_execute_batch", "panda_msm_batch_plan"))
     assert re.search(r"#define\s+PANDA_MSM_MAX_BATCH\s+%d\b" % MAX_BATCH, header)
 
 
@@ -102,13 +93,6 @@ def test_batch_plan_is_consistent_and_fuses_where_it_matters():
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
 def _decode(curve, raw, coord=pgm.JACOBIAN):
     """a result of the C ABI as a comparable affine point"""
     proj = coord == pgm.PROJECTIVE
@@ -129,12 +113,6 @@ def _expected(curve, seed_b, scalars):
         return pyref.g2_mul(k, pyref.G2_GEN)
     g2 = g381 if curve == 4 else g377
     return g2.mul(k, g2.GEN)
-
-
-def _scalar_wire(curve, v):
-    """v mod r as the 8 Montgomery-form words of the wire"""
-    r = pyref.limbs_to_int(po.field_info(INFO[curve][4])["p"])
-    return pyref.int_to_limbs(v % r * (1 << 256) % r, 8)
 
 
 class Batch:
@@ -261,7 +239,7 @@ def test_members_that_stress_the_sort(gm):
         n = b.n
         b.set_member(1, np.zeros((n, 8), np.uint32))
         b.set_member(3, np.tile(b.scalars[0][5], (n, 1)))
-        b.set_member(4, np.tile(_scalar_wire(0, -1), (n, 1)))
+        b.set_member(4, np.tile(fr.wire_one(0, -1), (n, 1)))
         b.set_member(5, b.scalars[0])
         last = np.zeros((n, 8), np.uint32)
         last[n - 1] = b.scalars[2][7]

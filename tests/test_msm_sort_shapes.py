@@ -11,8 +11,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
-import pyref
+from gpu_util import gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
@@ -26,19 +27,6 @@ INFO = {
 SETS = ("equal", "one_window", "zero", "r_minus_1", "alternating", "last_three", "uniform")
 
 
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
-def _wire(curve, v):
-    """v mod r as the 8 Montgomery-form words of the wire"""
-    r = pyref.limbs_to_int(po.field_info(INFO[curve][3])["p"])
-    return np.array(pyref.int_to_limbs(v % r * (1 << 256) % r, 8), dtype=np.uint32)
-
-
 def _scalar_set(curve, name, random_rows, window_bits):
     """(n, 8) wire-form scalars of set `name`; random_rows are uniform scalars of the same shape"""
     n = random_rows.shape[0]
@@ -49,7 +37,7 @@ def _scalar_set(curve, name, random_rows, window_bits):
     if name == "zero":
         return np.zeros((n, 8), np.uint32)
     if name == "r_minus_1":
-        return np.tile(_wire(curve, -1), (n, 1))
+        return np.tile(fr.wire_one(curve, -1), (n, 1))
     if name == "alternating":
         out = np.empty((n, 8), np.uint32)
         out[0::2] = random_rows[1 % n]
@@ -64,7 +52,7 @@ def _scalar_set(curve, name, random_rows, window_bits):
     # wide or one bit narrower), so the signed recoding neither carries nor borrows -- one non-zero window per scalar (two where the digit
     # straddles a boundary of a plan with two widths), every window in turn
     windows = 248 // window_bits
-    palette = np.stack([_wire(curve, (1 + (37 * j) % 100) << (window_bits * (j % windows))) for j in range(8 * windows)])
+    palette = np.stack([fr.wire_one(curve, (1 + (37 * j) % 100) << (window_bits * (j % windows))) for j in range(8 * windows)])
     return palette[np.arange(n) % len(palette)]
 
 
@@ -74,7 +62,7 @@ class Problem:
     def __init__(self, gm, curve, k, seed, members=1):
         from gpu_util import NULL_STREAM, DeviceBuffer
         self.lib, self.gm, self.curve, self.k, self.n, self.members, self.seed = ffi.load(), gm, curve, k, 1 << k, members, seed
-        self.entry, aff, self.res, fr = INFO[curve]
+        self.entry, aff, self.res, fid = INFO[curve]
         self.db, self.ds, self.dr = DeviceBuffer(self.n * aff), DeviceBuffer(members * self.n * 32), DeviceBuffer(members * self.res)
         ffi.check(self.lib.panda_gen_bases(curve, seed, 0, self.n, self.db.ptr, NULL_STREAM), "gen")
         ffi.check(self.lib.panda_msm_precompute_bases(curve, self.db.ptr, k, 0, gm.exec_stream.raw), "precompute")
@@ -82,7 +70,7 @@ class Problem:
         ffi.check(self.lib.panda_msm_registered_info(self.db.ptr, C.byref(tables), C.byref(bits), None), "info")
         assert tables.value >= 2 and bits.value >= 9, "the call must take the tabled path"
         self.window_bits = bits.value
-        self.random = po.gen_scalars(fr, seed + 1, self.n)
+        self.random = po.gen_scalars(fid, seed + 1, self.n)
 
     def upload(self, member, rows):
         rows = np.ascontiguousarray(rows, dtype=np.uint32)

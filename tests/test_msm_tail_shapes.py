@@ -21,19 +21,13 @@ import pytest
 
 import oracle as po
 import pyref
+from gpu_util import gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 from test_msm_sort_shapes import Problem, _scalar_set
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 gpu = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
 
 
 # ------------------------------------------------------------------ the tile map, on the host

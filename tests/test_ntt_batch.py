@@ -5,20 +5,18 @@ workgroup), with the single call's table set and one synchronisation.  NTT outpu
 is of whole buffers, byte for byte: against the CPU oracle where it is cheap, against the library's own single call (itself pinned to
 the oracle by test_gpu_parity.py) where it is not.  Both device buffers carry one guard member behind the batch, which no call may touch."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
 import pyref
+from gpu_util import GUARD, assert_exported, gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 MAX_BATCH = 4096  # PANDA_NTT_MAX_BATCH
 FORWARD, INVERSE, BITREV_OUT, INVERSE_BITREV_IN, COSET, COSET_INVERSE = range(6)
 KINDS = (FORWARD, INVERSE, BITREV_OUT, INVERSE_BITREV_IN, COSET, COSET_INVERSE)
@@ -48,14 +46,7 @@ def _kind_passes(lib, log_n, kind):
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in ("panda_ntt_execute_batch", "panda_ntt_batch_plan"):
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    header, _ = assert_exported(("panda_ntt_execute_batch", "panda_ntt_batch_plan"))
     assert re.search(r"#define\s+PANDA_NTT_MAX_BATCH\s+%d\b" % MAX_BATCH, header)
     assert ffi.NTT_MAX_BATCH == MAX_BATCH
     assert (ffi.NTT_FORWARD, ffi.NTT_INVERSE, ffi.NTT_BITREV_OUT, ffi.NTT_INVERSE_BITREV_IN, ffi.NTT_COSET, ffi.NTT_COSET_INVERSE) == KINDS
@@ -119,34 +110,6 @@ def test_batch_plan():
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
-def _modulus(field):
-    return pyref.limbs_to_int(po.field_info(po.FR_OF[field])["p"])
-
-
-def _wire(field, v):
-    """v mod r as the 8 Montgomery-form words of the wire"""
-    r = _modulus(field)
-    return np.array(pyref.int_to_limbs(v % r * (1 << 256) % r, 8), np.uint32)
-
-
-def _shift_powers(field, n):
-    """g^j, j < n, in Montgomery form"""
-    r = _modulus(field)
-    pw = np.empty((n, 8), np.uint32)
-    acc = 1
-    for j in range(n):
-        pw[j] = pyref.int_to_limbs(acc * (1 << 256) % r, 8)
-        acc = acc * SHIFT % r
-    return pw
-
-
 def _perm(log_n):
     return np.array([int(format(k, f"0{log_n}b")[::-1], 2) if log_n else 0 for k in range(1 << log_n)])
 
@@ -162,7 +125,7 @@ class Harness:
         self.a, self.b = DeviceBuffer((batch + 1) * self.mbytes), DeviceBuffer((batch + 1) * self.mbytes)
         self.sa, self.sb = DeviceBuffer(self.mbytes), DeviceBuffer(self.mbytes)
         self.omega = po.root_of_unity(self.fid, log_n)
-        self.g = _wire(field, SHIFT)
+        self.g = fr.wire_one(field, SHIFT)
         self.flag = C.c_uint(9)
 
     def cfg(self, src, dst, log_n=None):
@@ -177,15 +140,15 @@ class Harness:
         batch = self.batch if batch is None else batch
         data = np.ascontiguousarray(data, np.uint32).reshape(batch, self.n, 8)
         total = (self.batch + 1) * self.mbytes
-        ffi.check(self.lib.panda_memset(self.a.ptr, 0xA5, total), "memset")
-        ffi.check(self.lib.panda_memset(self.b.ptr, 0xA5, total), "memset")
+        ffi.check(self.lib.panda_memset(self.a.ptr, GUARD, total), "memset")
+        ffi.check(self.lib.panda_memset(self.b.ptr, GUARD, total), "memset")
         ffi.check(self.lib.panda_memcpy(self.a.ptr, C.c_void_p(data.ctypes.data), batch * self.mbytes), "memcpy")
         self.flag.value = 9
         ffi.check(self.lib.panda_ntt_execute_batch(self.field, kind, self.cfg(self.a.ptr, self.b.ptr), batch, self.shift_ptr(kind)), "batch")
         assert self.flag.value in (0, 1)
         for d in (self.a, self.b):
             guard = d.to_host(np.uint8, nbytes=total - batch * self.mbytes, offset=batch * self.mbytes)
-            assert (guard == 0xA5).all(), "bytes behind the batch were written"
+            assert (guard == GUARD).all(), "bytes behind the batch were written"
         res = self.b if self.flag.value else self.a
         return self.flag.value, res.to_host(np.uint32, nbytes=batch * self.mbytes).reshape(batch, self.n, 8)
 
@@ -296,7 +259,7 @@ def _other_kinds_vs_oracle(h, seed):
     flag, back = h.batch_call(INVERSE_BITREV_IN, got)
     assert flag == h.expected_flag(INVERSE_BITREV_IN)
     assert np.array_equal(back, x)
-    pw = _shift_powers(h.field, h.n)
+    pw = fr.shift_powers(h.field, h.n, SHIFT)
     scaled = np.stack([po.f_vec(h.fid, po.OP_MUL, np.ascontiguousarray(m), pw) for m in x])
     cwant = h.oracle(scaled)
     flag, got = h.batch_call(COSET, x)

@@ -9,27 +9,24 @@ COSET_MAJOR order is the permutation [(i, k)] <- [i + B k] of it.  All three dev
 pattern behind the batch, which no call may touch; the coefficients must come back unchanged too."""
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
 import pyref
+from gpu_util import GUARD, assert_exported, gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 MAX_BATCH = 4096  # PANDA_NTT_MAX_BATCH
 MAX_LOG_BLOWUP = 4  # PANDA_NTT_LDE_MAX_LOG_BLOWUP
 COSET_MAJOR, NATURAL = 0, 1
 ORDERS = (COSET_MAJOR, NATURAL)
 FIELD_NAME = ("bn254", "bls12_377", "bls12_381")
 SHIFT = 5  # the coset generator, as in test_ntt_batch.py
-GUARD = 0xA5
 
 
 def _plan(lib, log_n, log_blowup, batch, order):
@@ -46,14 +43,7 @@ def _passes(lib, log_n):
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in ("panda_ntt_execute_lde", "panda_ntt_lde_plan"):
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    header, _ = assert_exported(("panda_ntt_execute_lde", "panda_ntt_lde_plan"))
     assert re.search(r"#define\s+PANDA_NTT_LDE_MAX_LOG_BLOWUP\s+%d\b" % MAX_LOG_BLOWUP, header)
     assert re.search(r"#define\s+PANDA_NTT_LDE_COSET_MAJOR\s+%du\b" % COSET_MAJOR, header)
     assert re.search(r"#define\s+PANDA_NTT_LDE_NATURAL\s+%du\b" % NATURAL, header)
@@ -131,36 +121,6 @@ def test_lde_plan():
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
-def _modulus(field):
-    return pyref.limbs_to_int(po.field_info(po.FR_OF[field])["p"])
-
-
-def _wire(field, v):
-    """v mod r as the 8 Montgomery-form words of the wire"""
-    r = _modulus(field)
-    return np.array(pyref.int_to_limbs(v % r * (1 << 256) % r, 8), np.uint32)
-
-
-@functools.lru_cache(maxsize=None)
-def _shift_powers(field, n):
-    """g^j, j < n, in Montgomery form"""
-    r = _modulus(field)
-    pw = np.empty((n, 8), np.uint32)
-    acc = 1
-    for j in range(n):
-        pw[j] = pyref.int_to_limbs(acc * (1 << 256) % r, 8)
-        acc = acc * SHIFT % r
-    pw.setflags(write=False)
-    return pw
-
-
 def _to_coset_major(natural, log_n, log_blowup):
     """(batch, N, 8) in the NATURAL order -> the COSET_MAJOR order: element (i, k) is element i + B k"""
     batch = natural.shape[0]
@@ -179,7 +139,7 @@ def _oracle_natural(field, log_n, log_blowup, batch, seed):
     """the oracle's value, computed once per shape and shared by the two orders: zero-pad to N, multiply element j by g^j, transform"""
     fid, n, log_big = po.FR_OF[field], 1 << log_n, log_n + log_blowup
     omega = po.root_of_unity(fid, log_big)
-    pw = _shift_powers(field, n)
+    pw = fr.shift_powers(field, n, SHIFT)
     out = []
     for c in _coeffs(field, log_n, batch, seed):
         padded = np.zeros((1 << log_big, 8), np.uint32)
@@ -201,7 +161,7 @@ class Harness:
         self.c = DeviceBuffer((batch + 1) * self.cbytes)
         self.a, self.b = DeviceBuffer((batch + 1) * self.bytes), DeviceBuffer((batch + 1) * self.bytes)
         self.omega = po.root_of_unity(self.fid, log_n + log_blowup)
-        self.g = _wire(field, SHIFT)
+        self.g = fr.wire_one(field, SHIFT)
         self.flag = C.c_uint(9)
 
     def cfg(self, src, dst, log_n=None, omega=None):
@@ -407,9 +367,9 @@ def test_gpu_manager_helper(gm):
     omega = po.root_of_unity(po.F_BN254_FR, log_n + log_blowup)
     polys = [np.array(c) for c in x]
     for order, want in ((ffi.NTT_LDE_COSET_MAJOR, _to_coset_major(natural, log_n, log_blowup)), (ffi.NTT_LDE_NATURAL, natural)):
-        got = pgm.panda_ntt_gpu_lde(gm, polys, omega, log_n, log_blowup, _wire(0, SHIFT), order=order)
+        got = pgm.panda_ntt_gpu_lde(gm, polys, omega, log_n, log_blowup, fr.wire_one(0, SHIFT), order=order)
         assert len(got) == batch
         for j in range(batch):
             assert got[j].shape == (1 << (log_n + log_blowup), 8) and np.array_equal(got[j], want[j])
             assert np.array_equal(polys[j], x[j]), "the helper changed its input"
-    assert pgm.panda_ntt_gpu_lde(gm, [], omega, log_n, log_blowup, _wire(0, SHIFT)) == []
+    assert pgm.panda_ntt_gpu_lde(gm, [], omega, log_n, log_blowup, fr.wire_one(0, SHIFT)) == []

@@ -20,13 +20,14 @@ import os
 import numpy as np
 import pytest
 
+import field_ref as fr
 import ntt_patterns as pat
 import oracle as po
 import pyref
 import test_ntt_batch as tb
 import test_ntt_lde as tl
+from gpu_util import gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
-from panda_amd import gpu_manager as pgm
 
 FORWARD, INVERSE, BITREV_OUT, INVERSE_BITREV_IN, COSET, COSET_INVERSE = tb.KINDS
 INVERSE_OF = {FORWARD: INVERSE, BITREV_OUT: INVERSE_BITREV_IN, COSET: COSET_INVERSE}
@@ -72,13 +73,6 @@ def test_sizes_cover_every_kernel_instance():
 
 
 # ------------------------------------------------------------------------------------------------------------ expected values
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
 def _root(field, log_n):
     omega = po.root_of_unity(po.FR_OF[field], log_n)
     return omega, pyref.decode_scalar(pyref.CURVES[field], omega)
@@ -127,14 +121,14 @@ def _coset_oracle(field, log_n, which):
     """the oracle's transform of x[j] g^j"""
     cs = _case(field, log_n, which)
     fid = po.FR_OF[field]
-    pw = tl._shift_powers(field, 1 << log_n)
+    pw = fr.shift_powers(field, 1 << log_n, SHIFT)
     omega, _ = _root(field, log_n)
     return _oracle_many(fid, [po.f_vec(fid, po.OP_MUL, np.ascontiguousarray(m), pw) for m in cs.x], omega, log_n)
 
 
 def _wire_const(field, value, n):
     """`value` (a plain integer: a factor on wire values) as n rows of Montgomery-form words, the second operand of the oracle's product"""
-    return np.tile(tb._wire(field, value), (n, 1))
+    return np.tile(fr.wire_one(field, value), (n, 1))
 
 
 @functools.lru_cache(maxsize=8)
@@ -306,7 +300,7 @@ def test_lde(gm, field, log_n, log_blowup, order):
     coeffs[1, :] = top
     coeffs[2, n - 1] = top
     omega = po.root_of_unity(fid, log_big)
-    pw = tl._shift_powers(field, n)
+    pw = fr.shift_powers(field, n, SHIFT)
     padded = np.zeros((4, 1 << log_big, 8), np.uint32)
     for j in range(4):
         padded[j, :n] = po.f_vec(fid, po.OP_MUL, np.ascontiguousarray(coeffs[j]), pw)

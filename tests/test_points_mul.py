@@ -7,20 +7,18 @@ them): affine points on the wire, the identity as all-zero bytes.  Output coordi
 byte; there is no tolerance anywhere.  Every device buffer carries a guard run behind the data, which no call may touch; the inputs of
 an out-of-place call must come back unchanged.  tests/host_check/points_mul_host.cpp runs the per-thread routines under FE29_CHECK."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import pyref
+from gpu_util import assert_exported, gm, run_host_check  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
-from points_ref import CURVES, Dev, compare, enc, enc_all, enc_multiples, host_ptr, mul_g, point_bytes, random_scalars, scalar_wire, scalars_wire
+from points_ref import CURVES, Dev, compare, enc, enc_all, enc_multiples, host_ptr, mul_g, point_bytes
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NAMES = ("panda_points_scalar_mul", "panda_points_scalar_mul_plan", "panda_kzg_open_all_setup", "panda_kzg_open_all", "panda_kzg_open_all_plan")
 EACH, ONE, POWERS = 0, 1, 2
 MODES = (EACH, ONE, POWERS)
@@ -40,14 +38,7 @@ def _ptr(v):
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in NAMES:
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    header, _ = assert_exported(NAMES)
     for macro, value in (("PANDA_POINTS_MUL_EACH", "0u"), ("PANDA_POINTS_MUL_ONE", "1u"), ("PANDA_POINTS_MUL_POWERS", "2u"), ("PANDA_KZG_OPEN_ALL_MAX_LOG_N", "25")):
         assert re.search(r"#define\s+%s\s+%s\b" % (macro, value), header)
     assert (ffi.POINTS_MUL_EACH, ffi.POINTS_MUL_ONE, ffi.POINTS_MUL_POWERS, ffi.KZG_OPEN_ALL_MAX_LOG_N) == (0, 1, 2, 25)
@@ -74,7 +65,7 @@ def _refusals(lib, curve, P, A, OUT, SC, n, stream, untouched):
     """every refusal of the contract over valid buffers of n points at P, A and OUT and of n scalars at SC (disjoint, at least one point
     of room on either side of each); `untouched()` says that nothing was written"""
     pb, c = point_bytes(curve), pyref.CURVES[curve]
-    one, two = np.ascontiguousarray(scalar_wire(curve, 5)), np.ascontiguousarray(np.concatenate([scalar_wire(curve, 3), scalar_wire(curve, 7)]))
+    one, two = np.ascontiguousarray(fr.wire_one(curve, 5)), np.ascontiguousarray(np.concatenate([fr.wire_one(curve, 3), fr.wire_one(curve, 7)]))
     count = [0]
 
     def call(curve=curve, mode=EACH, pts=P, d_sc=SC, h_sc=None, add=A, out=OUT, n=n):
@@ -96,8 +87,8 @@ def _refusals(lib, curve, P, A, OUT, SC, n, stream, untouched):
     r_words, ones = pyref.int_to_limbs(c.r, 8), np.full(8, 0xFFFFFFFF, np.uint32)
     for bad in (r_words, ones):
         assert call(mode=ONE, d_sc=None, h_sc=np.ascontiguousarray(bad)) == 1
-        assert call(mode=POWERS, d_sc=None, h_sc=np.ascontiguousarray(np.concatenate([bad, scalar_wire(curve, 7)]))) == 1
-        assert call(mode=POWERS, d_sc=None, h_sc=np.ascontiguousarray(np.concatenate([scalar_wire(curve, 3), bad]))) == 1
+        assert call(mode=POWERS, d_sc=None, h_sc=np.ascontiguousarray(np.concatenate([bad, fr.wire_one(curve, 7)]))) == 1
+        assert call(mode=POWERS, d_sc=None, h_sc=np.ascontiguousarray(np.concatenate([fr.wire_one(curve, 3), bad]))) == 1
     # overlaps: the output over either input other than exactly, and the two inputs over each other (exactly included)
     for off in (pb, -pb, 16, -16, n * pb - 16, -(n * pb - 16)):
         assert call(out=P + off) == 1 and call(out=A + off) == 1 and call(out=P + off, add=None) == 1, ("overlap", off)
@@ -121,28 +112,17 @@ def test_host_program_checks_the_bounds_and_the_exceptional_cases(tmp_path):
     """tests/host_check/points_mul_host.cpp: scalar_bits, scalar_mul at every loop length from the scalar's own up to 256, add_affine_wire
     (A the identity, A = k P, A = -k P), scalar_from_wire and power_scalar of points_mul.h on the host under FE29_CHECK against the affine
     law in integer arithmetic of its own, for the three curves; every stored point is checked against the stored-point bounds"""
-    exe = str(tmp_path / "points_mul_host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-o", exe, os.path.join(HERE, "host_check", "points_mul_host.cpp")], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert re.fullmatch(r"ok (\d+)\n", out.stdout) and int(out.stdout.split()[1]) >= 50000
+    assert run_host_check(tmp_path, "points_mul_host.cpp") >= 50000
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
 def _mode_scalars(curve, mode, ks=None, one=None, c=None, s=None):
     """(device scalars to stage or None, host scalars or None) of a call"""
     if mode == EACH:
-        return scalars_wire(curve, ks), None
+        return fr.wire(curve, ks), None
     if mode == ONE:
-        return None, np.ascontiguousarray(scalar_wire(curve, one))
-    return None, np.ascontiguousarray(np.concatenate([scalar_wire(curve, c), scalar_wire(curve, s)]))
+        return None, np.ascontiguousarray(fr.wire_one(curve, one))
+    return None, np.ascontiguousarray(np.concatenate([fr.wire_one(curve, c), fr.wire_one(curve, s)]))
 
 
 def _run(gm, curve, mode, pts, d_sc, h_sc, add, n, what="", in_place=None):
@@ -170,8 +150,8 @@ class Fixture:
     def __init__(self, curve):
         c = pyref.CURVES[curve]
         self.curve, self.r = curve, c.r
-        self.a, self.b, self.k = (random_scalars(curve, 0x9A00 + 16 * curve + j, N) for j in range(3))
-        self.one, self.c, self.s = random_scalars(curve, 0x9A80 + curve, 3)
+        self.a, self.b, self.k = (fr.random_residues(curve, 0x9A00 + 16 * curve + j, N) for j in range(3))
+        self.one, self.c, self.s = fr.random_residues(curve, 0x9A80 + curve, 3)
         self.P, self.A = enc_multiples(curve, self.a), enc_multiples(curve, self.b)
 
     def scalars(self, mode):
@@ -221,7 +201,7 @@ def test_waves_with_different_loop_lengths(gm, curve):
             ks[3], ks[17] = 0, 1
         for addend in (False, True):
             want = enc_multiples(curve, [(f.b[i] if addend else 0) + ks[i] * f.a[i] for i in range(N)])
-            got = _run(gm, curve, EACH, f.P, scalars_wire(curve, ks), None, f.A if addend else None, N, (curve, first, addend))
+            got = _run(gm, curve, EACH, f.P, fr.wire(curve, ks), None, f.A if addend else None, N, (curve, first, addend))
             compare(got, want, (curve, first, addend))
 
 
@@ -232,8 +212,8 @@ def test_structured_inputs(gm, curve):
     x == 0 with a nonzero y as the input identity; in place over d_points and over d_addend"""
     f, c = _fixture(curve), pyref.CURVES[curve]
     zero = np.zeros_like(f.P)
-    each = lambda ks: scalars_wire(curve, ks)
-    host = lambda *vs: np.ascontiguousarray(np.concatenate([scalar_wire(curve, v) for v in vs]))
+    each = lambda ks: fr.wire(curve, ks)
+    host = lambda *vs: np.ascontiguousarray(np.concatenate([fr.wire_one(curve, v) for v in vs]))
     negP = enc_multiples(curve, [-a for a in f.a])
     # k = 0
     assert not _run(gm, curve, EACH, f.P, each([0] * N), None, None, N).any()
@@ -281,16 +261,16 @@ def test_across_workgroups(gm, curve):
     additions; 64 fixed outputs per mode against integers, and over the whole buffer k then k^-1 returns the input in every mode"""
     n, c = N_MANY, pyref.CURVES[curve]
     assert len(SAMPLES) == 64 and (n + 63) // 64 == 65 and (n + 15) // 16 > 256
-    a, d, one, cc, s = random_scalars(curve, 0x9A20 + curve, 5)
+    a, d, one, cc, s = fr.random_residues(curve, 0x9A20 + curve, 5)
     step, Q, pts = mul_g(curve, d), mul_g(curve, a), []
     for _ in range(n):
         pts.append(Q)
         Q = pyref.ec_add(c, Q, step)
     words = enc_all(curve, pts)
-    ks = random_scalars(curve, 0x9A30 + curve, n)
+    ks = fr.random_residues(curve, 0x9A30 + curve, n)
     inv = lambda v: pow(v, -1, c.r)
-    host = lambda *vs: np.ascontiguousarray(np.concatenate([scalar_wire(curve, v) for v in vs]))
-    cases = ((EACH, scalars_wire(curve, ks), None, scalars_wire(curve, [inv(k) for k in ks]), None, lambda i: ks[i]),
+    host = lambda *vs: np.ascontiguousarray(np.concatenate([fr.wire_one(curve, v) for v in vs]))
+    cases = ((EACH, fr.wire(curve, ks), None, fr.wire(curve, [inv(k) for k in ks]), None, lambda i: ks[i]),
              (ONE, None, host(one), None, host(inv(one)), lambda i: one),
              (POWERS, None, host(cc, s), None, host(inv(cc), inv(s)), lambda i: cc * pow(s, i, c.r)))
     for mode, d_sc, h_sc, d_back, h_back, k_of in cases:
@@ -309,7 +289,7 @@ def test_refusals_leave_the_guarded_buffers_untouched(gm):
         try:
             n, pb = 16, point_bytes(curve)
             f = _fixture(curve)
-            rooms = [h.buffer(np.concatenate([f.P[:48]])), h.buffer(np.concatenate([f.A[:48]])), h.buffer(scalars_wire(curve, f.k[:48]))]
+            rooms = [h.buffer(np.concatenate([f.P[:48]])), h.buffer(np.concatenate([f.A[:48]])), h.buffer(fr.wire(curve, f.k[:48]))]
             out = h.buffer(nbytes=48 * pb)
             P, A, SC, OUT = rooms[0].ptr.value + 16 * pb, rooms[1].ptr.value + 16 * pb, rooms[2].ptr.value + 16 * 32, out.ptr.value + 16 * pb
             untouched = lambda: all(h.intact(r) for r in rooms) and h.untouched(out)
@@ -333,11 +313,11 @@ def test_host_array_wrapper(gm):
     """panda_points_gpu_scalar_mul: host arrays in and out, the three modes"""
     curve = 0
     f = _fixture(curve)
-    got = pgm.panda_points_gpu_scalar_mul(gm, f.P, scalars_wire(curve, f.k), curve, addend=f.A)
+    got = pgm.panda_points_gpu_scalar_mul(gm, f.P, fr.wire(curve, f.k), curve, addend=f.A)
     compare(got.view(np.uint32).reshape(N, -1), enc_multiples(curve, [b + k * a for a, b, k in zip(f.a, f.b, f.k)]), "EACH")
-    got = pgm.panda_points_gpu_scalar_mul(gm, f.P, scalar_wire(curve, f.one), curve, mode=ffi.POINTS_MUL_ONE)
+    got = pgm.panda_points_gpu_scalar_mul(gm, f.P, fr.wire_one(curve, f.one), curve, mode=ffi.POINTS_MUL_ONE)
     compare(got.view(np.uint32).reshape(N, -1), enc_multiples(curve, [f.one * a for a in f.a]), "ONE")
-    got = pgm.panda_points_gpu_scalar_mul(gm, f.P, np.concatenate([scalar_wire(curve, 1), scalar_wire(curve, 1)]), curve, mode=ffi.POINTS_MUL_POWERS)
+    got = pgm.panda_points_gpu_scalar_mul(gm, f.P, np.concatenate([fr.wire_one(curve, 1), fr.wire_one(curve, 1)]), curve, mode=ffi.POINTS_MUL_POWERS)
     compare(got.view(np.uint32).reshape(N, -1), f.P, "POWERS")
     with pytest.raises(pgm.PandaGpuError):
-        pgm.panda_points_gpu_scalar_mul(gm, f.P, scalars_wire(curve, f.k[:5]), curve)
+        pgm.panda_points_gpu_scalar_mul(gm, f.P, fr.wire(curve, f.k[:5]), curve)

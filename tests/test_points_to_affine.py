@@ -11,11 +11,13 @@ import functools
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
 import pyref
+from gpu_util import gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
-from test_ec_ntt import CURVES, GUARD, Dev, _enc, _mul_g, _pb, _scalars, gm  # noqa: F401  (gm: the module's device fixture)
+from test_ec_ntt import CURVES, Dev, _enc, _mul_g, _pb
 
 gpu = pytest.mark.gpu
 CAP = 1 << 28
@@ -82,7 +84,7 @@ def test_bad_arguments_are_refused_before_any_device_call():
 def _points(curve, n):
     """(a + j d) G for j < n by repeated additions"""
     c = pyref.CURVES[curve]
-    a, d = _scalars(curve, 0xAF00 + curve, 2)
+    a, d = fr.random_residues(curve, 0xAF00 + curve, 2)
     step, P, pts = _mul_g(curve, d), _mul_g(curve, a), []
     for _ in range(n):
         pts.append(P)
@@ -181,7 +183,7 @@ def test_refusals_leave_the_guarded_output_untouched(gm):
             room = h.buffer(np.arange(3 * n * pb * 3 // 2 // 4, dtype=np.uint32))
             out = h.buffer(nbytes=3 * n * pb)
             IN, OUT = room.ptr.value + n * pb * 3 // 2, out.ptr.value + n * pb
-            untouched = lambda: h.intact(room) and bool((out.to_host(np.uint8) == GUARD).all())
+            untouched = lambda: h.intact(room) and h.untouched(out)
             assert _refusals(lib, curve, IN, OUT, n, h.stream, untouched) > 20
             short = DeviceBuffer(n * pb)
             try:

@@ -12,25 +12,23 @@ import ctypes as C
 import functools
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
 import pyref
+from gpu_util import GUARD, ROOT, GuardedBuffers, assert_exported, free_bytes, gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import model_poly_scan as mps  # noqa: E402
 
 MAX_POINTS = 8  # PANDA_POLY_MAX_POINTS
 MAX_ELEMS = 1 << 28
-GUARD, GUARD_BYTES = 0xA5, 4096
 
 
 def _plan(lib, n, batch):
@@ -52,41 +50,15 @@ def _second_level_sizes():
     return tile * chunk + 1, 2 * tile * chunk + tile + 5
 
 
-@functools.lru_cache(maxsize=None)
-def _modulus(field):
-    return pyref.limbs_to_int(po.field_info(po.FR_OF[field])["p"])
-
-
-def _wire(field, v):
-    """v mod r as the 8 Montgomery-form words of the wire"""
-    r = _modulus(field)
-    return np.array(pyref.int_to_limbs(v % r * (1 << 256) % r, 8), np.uint32)
-
-
-def _plain(field, wire):
-    r = _modulus(field)
-    return pyref.limbs_to_int(wire) * pow(1 << 256, -1, r) % r
-
-
-def _ints(a):
-    """(m, 8) uint32 -> m Python integers (the residues as they stand on the wire)"""
-    raw = np.ascontiguousarray(a, np.uint32).reshape(-1, 8).tobytes()
-    return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
-
-
-def _words(vals):
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), np.uint32).reshape(-1, 8)
-
-
 def _horner(field, coeffs, z_plain):
     """(quotient words (n, 8), remainder words (8,)) of one polynomial by plain Horner over Python integers"""
-    r = _modulus(field)
-    c = _ints(coeffs)
+    r = fr.modulus(field)
+    c = fr.ints(coeffs)
     q, s = [0] * len(c), 0
     for j in range(len(c) - 1, -1, -1):
         q[j] = s
         s = (c[j] + z_plain * s) % r
-    return _words(q), _words([s])[0]
+    return fr.words(q), fr.words([s])[0]
 
 
 def _is_quotient(field, coeffs, z_wire, q, rem):
@@ -105,14 +77,7 @@ def _is_quotient(field, coeffs, z_wire, q, rem):
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in ("panda_poly_evaluate", "panda_poly_divide_linear", "panda_poly_plan"):
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    header, lib = assert_exported(("panda_poly_evaluate", "panda_poly_divide_linear", "panda_poly_plan"))
     assert re.search(r"#define\s+PANDA_POLY_MAX_POINTS\s+%d\b" % MAX_POINTS, header)
     assert ffi.POLY_MAX_POINTS == MAX_POINTS
     assert lib.panda_poly_evaluate.argtypes[2] is C.c_uint64 and lib.panda_poly_divide_linear.argtypes[3] is C.c_uint64
@@ -130,8 +95,8 @@ def test_bad_arguments_are_refused_before_any_device_call():
     out = np.full((4 * MAX_POINTS, 8), 0x5A5A5A5A, np.uint32)
     outp = C.c_void_p(out.ctypes.data)
     for field in range(3):
-        r = _modulus(field)
-        good = np.stack([_wire(field, 3 + k) for k in range(MAX_POINTS)])
+        r = fr.modulus(field)
+        good = np.stack([fr.wire_one(field, 3 + k) for k in range(MAX_POINTS)])
         at_modulus = np.array(pyref.int_to_limbs(r, 8), np.uint32)
         all_ones = np.full(8, 0xFFFFFFFF, np.uint32)
         gp = C.c_void_p(good.ctypes.data)
@@ -213,13 +178,6 @@ def test_scan_model_agrees_with_plain_horner():
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
 @functools.lru_cache(maxsize=None)
 def _coeffs(field, n, batch, seed):
     x = po.gen_scalars(po.FR_OF[field], seed, batch * n).reshape(batch, n, 8)
@@ -231,61 +189,49 @@ def _coeffs(field, n, batch, seed):
 def _point(field, seed):
     """(wire words, plain integer) of a random point"""
     w = po.gen_scalars(po.FR_OF[field], 0x9000 + seed, 1)[0]
-    return w, _plain(field, w)
+    return w, fr.plain(field, w)[0]
 
 
-class Harness:
+class Harness(GuardedBuffers):
     """the coefficient and the quotient buffer, each with a guard run behind the batch"""
 
     def __init__(self, gm, field, n, batch):
-        from gpu_util import DeviceBuffer
+        super().__init__()
         self.lib, self.gm, self.field, self.n, self.batch = ffi.load(), gm, field, n, batch
         self.bytes = batch * n * 32
-        self.c, self.q = DeviceBuffer(self.bytes + GUARD_BYTES), DeviceBuffer(self.bytes + GUARD_BYTES)
+        self.c, self.q = self.buffer(nbytes=self.bytes), self.buffer(nbytes=self.bytes)
         self.stream = gm.exec_stream.raw
 
-    def fill(self, coeffs):
-        coeffs = np.ascontiguousarray(coeffs, np.uint32).reshape(self.batch, self.n, 8)
-        for d in (self.c, self.q):
-            ffi.check(self.lib.panda_memset(d.ptr, GUARD, self.bytes + GUARD_BYTES), "memset")
-        ffi.check(self.lib.panda_memcpy(self.c.ptr, C.c_void_p(coeffs.ctypes.data), self.bytes), "memcpy")
-        return coeffs
-
-    def guards_ok(self):
-        return all((d.to_host(np.uint8, nbytes=GUARD_BYTES, offset=self.bytes) == GUARD).all() for d in (self.c, self.q))
-
-    def coeffs_back(self):
-        return self.c.to_host(np.uint32, nbytes=self.bytes).reshape(self.batch, self.n, 8)
+    def load(self, coeffs):
+        """both buffers afresh, the coefficients (batch x n elements) in the first"""
+        assert np.asarray(coeffs).nbytes == self.bytes
+        self.fill(self.c, coeffs)
+        self.fill(self.q)
 
     def divide(self, coeffs, z_wire, in_place=False, remainders=True):
         """one panda_poly_divide_linear -> (quotients (batch, n, 8), remainders (batch, 8) or None); checks guards and coefficients"""
-        coeffs = self.fill(coeffs)
+        self.load(coeffs)
         z = np.ascontiguousarray(z_wire, np.uint32)
         rem = np.full((self.batch, 8), 0x77777777, np.uint32) if remainders else None
         dst = self.c if in_place else self.q
         ffi.check(self.lib.panda_poly_divide_linear(self.field, self.c.ptr, dst.ptr, self.n, self.batch, C.c_void_p(z.ctypes.data),
                                                     C.c_void_p(rem.ctypes.data) if remainders else None, self.stream), "divide")
-        assert self.guards_ok(), "bytes behind the batch were written"
+        assert self.guard_intact(self.c) and self.guard_intact(self.q), "bytes behind the batch were written"
         if in_place:
-            assert (self.q.to_host(np.uint8) == GUARD).all(), "the other buffer was written by a division in place"
+            assert self.untouched(self.q), "the other buffer was written by a division in place"
         else:
-            assert np.array_equal(self.coeffs_back(), coeffs), "d_coeffs was written"
-        return dst.to_host(np.uint32, nbytes=self.bytes).reshape(self.batch, self.n, 8), rem
+            assert self.intact(self.c), "d_coeffs was written"
+        return self.get(dst).reshape(self.batch, self.n, 8), rem
 
     def evaluate(self, coeffs, points_wire):
-        coeffs = self.fill(coeffs)
+        self.load(coeffs)
         pts = np.ascontiguousarray(points_wire, np.uint32).reshape(-1, 8)
         vals = np.full((self.batch, len(pts), 8), 0x77777777, np.uint32)
         ffi.check(self.lib.panda_poly_evaluate(self.field, self.c.ptr, self.n, self.batch, C.c_void_p(pts.ctypes.data), len(pts),
                                                C.c_void_p(vals.ctypes.data), self.stream), "evaluate")
-        assert self.guards_ok(), "bytes behind the batch were written"
-        assert np.array_equal(self.coeffs_back(), coeffs), "d_coeffs was written"
-        assert (self.q.to_host(np.uint8) == GUARD).all(), "an evaluation wrote to an unrelated buffer"
+        assert self.intact(self.c), "d_coeffs or the bytes behind the batch were written"
+        assert self.untouched(self.q), "an evaluation wrote to an unrelated buffer"
         return vals
-
-    def close(self):
-        self.c.free()
-        self.q.free()
 
 
 def _check_against_horner(h, coeffs, z_wire, z_plain, **kw):
@@ -365,16 +311,16 @@ def test_division_2_24(gm):
 @pytest.mark.parametrize("case", ["z0", "z1", "zm1", "allm1", "zero"])
 def test_edge_values(gm, case):
     tile, _ = _shape()
-    n, batch, r = tile + 1, 2, _modulus(0)
+    n, batch, r = tile + 1, 2, fr.modulus(0)
     coeffs = _coeffs(0, n, batch, 0xC000)
     z_plain = {"z0": 0, "z1": 1, "zm1": r - 1, "allm1": r - 1, "zero": _point(0, 5)[1]}[case]
     if case == "allm1":
-        coeffs = np.broadcast_to(_wire(0, r - 1), (batch, n, 8))
+        coeffs = np.broadcast_to(fr.wire_one(0, r - 1), (batch, n, 8))
     if case == "zero":
         coeffs = np.zeros((batch, n, 8), np.uint32)
     h = Harness(gm, 0, n, batch)
     try:
-        q, rem = _check_against_horner(h, coeffs, _wire(0, z_plain), z_plain)
+        q, rem = _check_against_horner(h, coeffs, fr.wire_one(0, z_plain), z_plain)
         if case == "z0":  # q_j = c_(j+1), r = c_0
             assert np.array_equal(q[:, :n - 1], coeffs[:, 1:]) and np.array_equal(rem, coeffs[:, 0])
         if case == "zero":
@@ -412,14 +358,14 @@ def test_partial_overlap_of_live_buffers_is_refused(gm):
     z_wire, _ = _point(0, 9)
     h = Harness(gm, 0, n, batch)
     try:
-        coeffs = h.fill(_coeffs(0, n, batch, 0xD100))
+        h.load(_coeffs(0, n, batch, 0xD100))
         rem = np.full((batch, 8), 0x77777777, np.uint32)
         zp, rp = C.c_void_p(z_wire.ctypes.data), C.c_void_p(rem.ctypes.data)
         for c_off, q_off in ((0, 32), (32, 0), (0, h.bytes - 32)):
             rc = h.lib.panda_poly_divide_linear(0, C.c_void_p(h.c.ptr.value + c_off), C.c_void_p(h.c.ptr.value + q_off), n, batch, zp, rp, h.stream)
             assert rc == 1
         assert (rem == 0x77777777).all()
-        assert np.array_equal(h.coeffs_back(), coeffs) and h.guards_ok() and (h.q.to_host(np.uint8) == GUARD).all()
+        assert h.intact(h.c) and h.untouched(h.q)
     finally:
         h.close()
 
@@ -457,15 +403,15 @@ def test_evaluation_at_roots_of_unity_equals_the_transform(gm):
     """f(w^k) is element k of the forward transform: ties the feature to panda_ntt_execute_bn254_v1, which the oracle pins"""
     from gpu_util import DeviceBuffer
     log_n, fid = 12, po.F_BN254_FR
-    n, r = 1 << log_n, _modulus(0)
+    n, r = 1 << log_n, fr.modulus(0)
     omega = po.root_of_unity(fid, log_n)
-    w = _plain(0, omega)
+    w = fr.plain(0, omega)[0]
     ks = (1, 777, n - 1)
     coeffs = _coeffs(0, n, 1, 0xE100)
     h = Harness(gm, 0, n, 1)
     sa, sb = DeviceBuffer(n * 32), DeviceBuffer(n * 32)
     try:
-        vals = h.evaluate(coeffs, np.stack([_wire(0, pow(w, k, r)) for k in ks]))
+        vals = h.evaluate(coeffs, np.stack([fr.wire_one(0, pow(w, k, r)) for k in ks]))
         flag = C.c_uint(9)
         ffi.check(h.lib.panda_memcpy(sa.ptr, C.c_void_p(np.ascontiguousarray(coeffs[0]).ctypes.data), n * 32), "memcpy")
         cfg = ffi.NttconfigurationV1(gm.mem_pool, gm.exec_stream.raw, sa.ptr, sb.ptr, C.c_void_p(omega.ctypes.data), log_n, C.pointer(flag))
@@ -525,7 +471,8 @@ def test_short_device_buffers_are_refused(gm):
     h = Harness(gm, 0, n, batch)
     short = DeviceBuffer(h.bytes - 32)  # one element short
     try:
-        coeffs = h.fill(_coeffs(0, n, batch, 0xF200))
+        coeffs = _coeffs(0, n, batch, 0xF200)
+        h.load(coeffs)
         ffi.check(h.lib.panda_memset(short.ptr, GUARD, h.bytes - 32), "memset")
         out = np.full((batch, 8), 0x77777777, np.uint32)
         zp, op = C.c_void_p(z_wire.ctypes.data), C.c_void_p(out.ctypes.data)
@@ -534,18 +481,11 @@ def test_short_device_buffers_are_refused(gm):
         assert h.lib.panda_poly_divide_linear(0, short.ptr, short.ptr, n, batch, zp, op, h.stream) == 1
         assert h.lib.panda_poly_evaluate(0, short.ptr, n, batch, zp, 1, op, h.stream) == 1
         assert (out == 0x77777777).all()
-        assert (short.to_host(np.uint8) == GUARD).all() and (h.q.to_host(np.uint8) == GUARD).all(), "a refused call wrote to a buffer"
-        assert np.array_equal(h.coeffs_back(), coeffs) and h.guards_ok()
+        assert (short.to_host(np.uint8) == GUARD).all() and h.untouched(h.q) and h.intact(h.c), "a refused call wrote to a buffer"
         _check_against_horner(h, coeffs, z_wire, z_plain)
     finally:
         short.free()
         h.close()
-
-
-def _free_bytes(lib):
-    free, total = C.c_size_t(0), C.c_size_t(0)
-    ffi.check(lib.panda_mem_get_info(C.byref(free), C.byref(total)), "mem_info")
-    return free.value
 
 
 @pytest.mark.gpu
@@ -558,16 +498,16 @@ def test_scratch_is_reused_and_released(gm):
     try:
         h.divide(coeffs, z_wire)  # whatever the runtime keeps from a kernel's first launch is there before the baseline is read
         ffi.check(h.lib.panda_ntt_tear_down(), "tear_down")
-        before = _free_bytes(h.lib)
+        before = free_bytes(h.lib)
         q1, r1 = h.divide(coeffs, z_wire)
-        first = _free_bytes(h.lib)
+        first = free_bytes(h.lib)
         q2, r2 = h.divide(coeffs, z_wire)
-        assert _free_bytes(h.lib) == first, "a repeated identical call allocated"
+        assert free_bytes(h.lib) == first, "a repeated identical call allocated"
         v = h.evaluate(coeffs, z_wire)  # needs no more scratch than the division
-        assert _free_bytes(h.lib) == first
+        assert free_bytes(h.lib) == first
         assert np.array_equal(q1, q2) and np.array_equal(r1, r2) and np.array_equal(v[:, 0], r1)
         ffi.check(h.lib.panda_ntt_tear_down(), "tear_down")
-        assert _free_bytes(h.lib) == before, "panda_ntt_tear_down releases the scratch"
+        assert free_bytes(h.lib) == before, "panda_ntt_tear_down releases the scratch"
     finally:
         h.close()
 

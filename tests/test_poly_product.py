@@ -12,26 +12,21 @@ fixed byte pattern behind the data, which no call may touch; inputs must come ba
 import ctypes as C
 import functools
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
-import pyref
+from gpu_util import GUARD, ROOT, GuardedBuffers, assert_exported, free_bytes, gm  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import model_poly_product as mpp  # noqa: E402
 
 MAX_ELEMS = 1 << 28
-GUARD, GUARD_BYTES = 0xA5, 4096
-W = 1 << 256
 NAMES = ("panda_field_batch_inverse", "panda_poly_grand_product", "panda_poly_product_plan")
 
 
@@ -49,25 +44,6 @@ def _shape():
     return ti, tp, chunk
 
 
-@functools.lru_cache(maxsize=None)
-def _modulus(field):
-    return pyref.limbs_to_int(po.field_info(po.FR_OF[field])["p"])
-
-
-def _wire(field, v):
-    r = _modulus(field)
-    return np.array(pyref.int_to_limbs(v % r * W % r, 8), np.uint32)
-
-
-def _ints(a):
-    raw = np.ascontiguousarray(a, np.uint32).reshape(-1, 8).tobytes()
-    return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
-
-
-def _words(vals):
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), np.uint32).reshape(-1, 8)
-
-
 def _no_zero(a):
     """no element of the (..., 8) array is zero"""
     return bool(np.any(np.asarray(a).reshape(-1, 8), axis=1).all())
@@ -78,29 +54,29 @@ def _zero_rows(a):
 
 
 def _inverse_expected(field, x):
-    r = _modulus(field)
-    w2 = W * W % r
-    return _words([pow(w, -1, r) * w2 % r if w else 0 for w in _ints(x)])
+    r = fr.modulus(field)
+    w2 = fr.W * fr.W % r
+    return fr.words([pow(w, -1, r) * w2 % r if w else 0 for w in fr.ints(x)])
 
 
 def _product_expected(field, num, den):
     """(Z words (n, 8), total words (8,)) of one vector; den None: the running product of num; a zero denominator: all zero"""
-    r = _modulus(field)
-    nw = _ints(num)
-    dw = [W % r] * len(nw) if den is None else _ints(den)
+    r = fr.modulus(field)
+    nw = fr.ints(num)
+    dw = [fr.W % r] * len(nw) if den is None else fr.ints(den)
     if 0 in dw:
         return np.zeros((len(nw), 8), np.uint32), np.zeros(8, np.uint32)
-    z, acc = [], W % r
+    z, acc = [], fr.W % r
     for a, b in zip(nw, dw):
         z.append(acc)
         acc = acc * a % r * pow(b, -1, r) % r
-    return _words(z), _words([acc])[0]
+    return fr.words(z), fr.words([acc])[0]
 
 
 def _is_inverse(field, x, out):
     fid = po.FR_OF[field]
     zero = ~np.any(x, axis=1)
-    want = np.where(zero[:, None], np.uint32(0), _wire(field, 1)[None, :]).astype(np.uint32)
+    want = np.where(zero[:, None], np.uint32(0), fr.wire_one(field, 1)[None, :]).astype(np.uint32)
     return np.array_equal(po.f_vec(fid, po.OP_MUL, out, x), want) and not out[zero].any()
 
 
@@ -108,7 +84,7 @@ def _is_product(field, num, den, out, total):
     """the complete characterisation for a vector without a zero denominator (den None: the wire's one)"""
     fid = po.FR_OF[field]
     n = len(num)
-    one = _wire(field, 1)
+    one = fr.wire_one(field, 1)
     if den is None:
         den = np.broadcast_to(one, (n, 8))
     if not np.array_equal(out[0], one):
@@ -120,14 +96,7 @@ def _is_product(field, num, den, out, total):
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in NAMES:
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    _, lib = assert_exported(NAMES)
     assert lib.panda_field_batch_inverse.argtypes[3] is C.c_uint64 and lib.panda_poly_grand_product.argtypes[4] is C.c_uint64
     assert lib.panda_poly_product_plan.argtypes[0] is C.c_uint64
 
@@ -230,13 +199,6 @@ def test_model_agrees_with_the_plain_definitions():
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
 @functools.lru_cache(maxsize=None)
 def _vectors(field, n, batch, seed):
     """(batch, n, 8) random scalars without a zero among them"""
@@ -246,69 +208,57 @@ def _vectors(field, n, batch, seed):
     return x
 
 
-class Harness:
-    """three device buffers of batch x n elements (a, b, o), each with a guard run behind the data"""
+class Harness(GuardedBuffers):
+    """three guarded device buffers of batch x n elements (a, b, o)"""
 
     def __init__(self, gm, field, n, batch=1):
-        from gpu_util import DeviceBuffer
+        super().__init__()
         self.lib, self.field, self.n, self.batch = ffi.load(), field, n, batch
         self.bytes = batch * n * 32
-        self.a, self.b, self.o = (DeviceBuffer(self.bytes + GUARD_BYTES) for _ in range(3))
+        self.a, self.b, self.o = (self.buffer(nbytes=self.bytes) for _ in range(3))
         self.stream = gm.exec_stream.raw
 
-    def _put(self, d, x):
-        ffi.check(self.lib.panda_memset(d.ptr, GUARD, self.bytes + GUARD_BYTES), "memset")
-        if x is not None:
-            x = np.ascontiguousarray(x, np.uint32).reshape(self.batch, self.n, 8)
-            ffi.check(self.lib.panda_memcpy(d.ptr, C.c_void_p(x.ctypes.data), self.bytes), "memcpy")
-        return x
+    def load(self, a, b=None):
+        """the three buffers afresh, with batch x n elements in a and, if given, in b"""
+        assert all(x is None or np.asarray(x).nbytes == self.bytes for x in (a, b))
+        self.fill(self.a, a)
+        self.fill(self.b, b)
+        self.fill(self.o)
 
-    def _get(self, d):
-        return d.to_host(np.uint32, nbytes=self.bytes).reshape(self.batch, self.n, 8)
-
-    def _guard_ok(self, d):
-        return (d.to_host(np.uint8, nbytes=GUARD_BYTES, offset=self.bytes) == GUARD).all()
-
-    def _untouched(self, d):
-        return (d.to_host(np.uint8) == GUARD).all()
+    def rows(self, d):
+        return self.get(d).reshape(self.batch, self.n, 8)
 
     def inverse(self, x, in_place=False):
         """one panda_field_batch_inverse over the batch x n elements end to end -> (batch, n, 8); checks guards and the input"""
-        x = self._put(self.a, x)
-        self._put(self.b, None)
-        self._put(self.o, None)
+        self.load(x)
         dst = self.a if in_place else self.o
         ffi.check(self.lib.panda_field_batch_inverse(self.field, self.a.ptr, dst.ptr, self.batch * self.n, self.stream), "inverse")
-        assert self._guard_ok(self.a) and self._guard_ok(self.o) and self._untouched(self.b), "bytes outside the output were written"
+        assert self.guard_intact(self.a) and self.guard_intact(self.o) and self.untouched(self.b), "bytes outside the output were written"
         if in_place:
-            assert self._untouched(self.o)
+            assert self.untouched(self.o)
         else:
-            assert np.array_equal(self._get(self.a), x), "d_in was written"
-        return self._get(dst)
+            assert self.intact(self.a), "d_in was written"
+        return self.rows(dst)
 
     def product(self, num, den, where="o", totals=True, den_is_num=False):
         """one panda_poly_grand_product -> (out (batch, n, 8), totals (batch, 8) or None); where: the buffer d_out is ("o", "a" = d_num,
         "b" = d_den); den None: d_den == NULL; den_is_num: d_den is d_num's pointer"""
-        num = self._put(self.a, num)
-        den = self._put(self.b, None if den_is_num else den)
-        self._put(self.o, None)
+        if den_is_num:
+            den = None
+        self.load(num, den)
         dst = {"o": self.o, "a": self.a, "b": self.b}[where]
         d_den = self.a.ptr if den_is_num else (self.b.ptr if den is not None else None)
         tot = np.full((self.batch, 8), 0x77777777, np.uint32) if totals else None
         ffi.check(self.lib.panda_poly_grand_product(self.field, self.a.ptr, d_den, dst.ptr, self.n, self.batch, C.c_void_p(tot.ctypes.data) if totals else None,
                                                     self.stream), "grand_product")
-        assert all(self._guard_ok(d) for d in (self.a, self.b, self.o)), "bytes behind the batch were written"
+        assert all(self.guard_intact(d) for d in (self.a, self.b, self.o)), "bytes behind the batch were written"
         if where != "a":
-            assert np.array_equal(self._get(self.a), num), "d_num was written"
+            assert self.intact(self.a), "d_num was written"
         if where != "b":
-            assert self._untouched(self.b) if den is None else np.array_equal(self._get(self.b), den), "d_den was written"
+            assert self.untouched(self.b) if den is None else self.intact(self.b), "d_den was written"
         if where != "o":
-            assert self._untouched(self.o), "the third buffer was written by a call in place"
-        return self._get(dst), tot
-
-    def close(self):
-        for d in (self.a, self.b, self.o):
-            d.free()
+            assert self.untouched(self.o), "the third buffer was written by a call in place"
+        return self.rows(dst), tot
 
 
 def _check_product(h, num, den, out, tot, by_identity=False):
@@ -457,8 +407,8 @@ def test_product_with_planted_zeros(gm):
 @pytest.mark.parametrize("case", ["ones", "minus_ones", "num_is_den_one_pointer", "num_is_den_two_buffers"])
 def test_edge_values(gm, case):
     tile = max(_shape()[:2])
-    n, batch, r = tile + 2, 2, _modulus(0)
-    one, m1 = _wire(0, 1), _wire(0, r - 1)
+    n, batch, r = tile + 2, 2, fr.modulus(0)
+    one, m1 = fr.wire_one(0, 1), fr.wire_one(0, r - 1)
     h = Harness(gm, 0, n, batch)
     try:
         if case in ("ones", "minus_ones"):
@@ -491,7 +441,7 @@ def test_the_permutation_argument(gm):
     h = Harness(gm, 0, n, batch)
     try:
         out, tot = h.product(num, den)
-        assert np.array_equal(tot, np.broadcast_to(_wire(0, 1), (batch, 8)))
+        assert np.array_equal(tot, np.broadcast_to(fr.wire_one(0, 1), (batch, 8)))
         _check_product(h, num, den, out, tot)
     finally:
         h.close()
@@ -566,9 +516,7 @@ def test_partial_overlaps_and_short_buffers_are_refused(gm):
     h = Harness(gm, 0, n, batch)
     short = DeviceBuffer(h.bytes - 32)  # one element short
     try:
-        h._put(h.a, num)
-        h._put(h.b, den)
-        h._put(h.o, None)
+        h.load(num, den)
         ffi.check(h.lib.panda_memset(short.ptr, GUARD, h.bytes - 32), "memset")
         tot = np.full((batch, 8), 0x77777777, np.uint32)
         tp = C.c_void_p(tot.ctypes.data)
@@ -584,8 +532,7 @@ def test_partial_overlaps_and_short_buffers_are_refused(gm):
         assert gp(short.ptr, h.b.ptr, h.o.ptr) == 1 and gp(h.a.ptr, short.ptr, h.o.ptr) == 1 and gp(h.a.ptr, h.b.ptr, short.ptr) == 1
         assert gp(short.ptr, None, short.ptr) == 1
         assert (tot == 0x77777777).all()
-        assert (short.to_host(np.uint8) == GUARD).all() and h._untouched(h.o), "a refused call wrote to a buffer"
-        assert np.array_equal(h._get(h.a), num) and np.array_equal(h._get(h.b), den) and h._guard_ok(h.a) and h._guard_ok(h.b)
+        assert (short.to_host(np.uint8) == GUARD).all() and h.untouched(h.o) and h.intact(h.a) and h.intact(h.b), "a refused call wrote to a buffer"
         _check_product(h, num, den, *h.product(num, den))
     finally:
         short.free()
@@ -633,12 +580,6 @@ def test_other_fields_at_the_second_level(gm, field):
     _second_level_product(gm, field, 0, 2)
 
 
-def _free_bytes(lib):
-    free, total = C.c_size_t(0), C.c_size_t(0)
-    ffi.check(lib.panda_mem_get_info(C.byref(free), C.byref(total)), "mem_info")
-    return free.value
-
-
 @pytest.mark.gpu
 def test_scratch_is_reused_and_released(gm):
     tile = _shape()[1]
@@ -649,16 +590,16 @@ def test_scratch_is_reused_and_released(gm):
         h.product(num, den)  # whatever the runtime keeps from a kernel's first launch is there before the baseline is read
         h.inverse(num)
         ffi.check(h.lib.panda_ntt_tear_down(), "tear_down")
-        before = _free_bytes(h.lib)
+        before = free_bytes(h.lib)
         o1, t1 = h.product(num, den)
-        first = _free_bytes(h.lib)
+        first = free_bytes(h.lib)
         o2, t2 = h.product(num, den)
-        assert _free_bytes(h.lib) == first, "a repeated identical call allocated"
+        assert free_bytes(h.lib) == first, "a repeated identical call allocated"
         h.inverse(num)  # batch x n elements: needs no more scratch than the product
-        assert _free_bytes(h.lib) == first
+        assert free_bytes(h.lib) == first
         assert np.array_equal(o1, o2) and np.array_equal(t1, t2)
         ffi.check(h.lib.panda_ntt_tear_down(), "tear_down")
-        assert _free_bytes(h.lib) == before, "panda_ntt_tear_down releases the scratch"
+        assert free_bytes(h.lib) == before, "panda_ntt_tear_down releases the scratch"
     finally:
         h.close()
 

@@ -10,23 +10,18 @@ anywhere.  T, the elements one workgroup covers, comes from the plan call.  Ever
 pattern behind the data, which no call may touch; inputs must come back unchanged unless they are the output."""
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import field_ref as fr
 import oracle as po
-import pyref
+from gpu_util import GUARD, GuardedBuffers, assert_exported, free_bytes, gm, run_host_check  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 MAX_ELEMS = 1 << 28
-GUARD, GUARD_BYTES = 0xA5, 4096
-W = 1 << 256
 NAMES = ("panda_poly_sum_of_products", "panda_poly_sum_of_products_plan")
 
 
@@ -43,52 +38,14 @@ def _tile():
     return tile
 
 
-@functools.lru_cache(maxsize=None)
-def _modulus(field):
-    return pyref.limbs_to_int(po.field_info(po.FR_OF[field])["p"])
-
-
-def _words(vals):
-    """256-bit integers -> (len, 8) uint32"""
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), np.uint32).reshape(-1, 8)
-
-
-def _ints(a):
-    raw = np.ascontiguousarray(a, np.uint32).reshape(-1, 8).tobytes()
-    return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
-
-
-def _wire(field, vals):
-    """plain residues -> wire words"""
-    r = _modulus(field)
-    return _words([v % r * W % r for v in vals])
-
-
-def _plain(field, a):
-    r = _modulus(field)
-    winv = pow(W, -1, r)
-    return [w * winv % r for w in _ints(a)]
-
-
-def _random(field, seed, batch, n, nonzero=False):
-    """(batch, n) plain residues as nested lists"""
-    r = _modulus(field)
-    rng = np.random.default_rng(seed)
-    raw = rng.bytes(40 * batch * n)
-    vals = [int.from_bytes(raw[40 * j:40 * j + 40], "little") % r for j in range(batch * n)]
-    if nonzero:
-        vals = [v or 1 for v in vals]
-    return [vals[p * n:(p + 1) * n] for p in range(batch)]
-
-
 def _col_words(field, col):
     """(batch, n) plain residues -> (batch, n, 8) wire words"""
-    return _wire(field, [v for row in col for v in row]).reshape(len(col), len(col[0]), 8)
+    return fr.wire(field, [v for row in col for v in row]).reshape(len(col), len(col[0]), 8)
 
 
 def _expected(field, cols, terms, scales=None, mode=0):
     """the definition over plain residues; cols[c][p][i], terms = [(coeff, [(column, rotation), ...]), ...] -> (batch, n, 8) wire words"""
-    r = _modulus(field)
+    r = fr.modulus(field)
     batch, n = len(cols[0]), len(cols[0][0])
     out = []
     for p in range(batch):
@@ -101,7 +58,7 @@ def _expected(field, cols, terms, scales=None, mode=0):
                 acc += t
             s = 1 if mode == 0 else scales[(p if mode == 1 else i) % len(scales)]
             out.append(acc * s % r)
-    return _wire(field, out).reshape(batch, n, 8)
+    return fr.wire(field, out).reshape(batch, n, 8)
 
 
 GATE = [(1, [(0, 0), (5, 0)]), (1, [(1, 0), (6, 0)]), (1, [(2, 0), (5, 0), (6, 0)]), (1, [(3, 0), (7, 0)]), (1, [(4, 0)])]  # q_L q_R q_M q_O q_C a b c
@@ -112,11 +69,11 @@ class Expression:
 
     def __init__(self, field, ptrs, terms, scales=None, mode=0, n_scales=None, wire_coeffs=None):
         self.ptrs = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
-        self.coeffs = np.ascontiguousarray(wire_coeffs if wire_coeffs is not None else _wire(field, [k for k, _ in terms]))
+        self.coeffs = np.ascontiguousarray(wire_coeffs if wire_coeffs is not None else fr.wire(field, [k for k, _ in terms]))
         self.degrees = (C.c_uint * max(len(terms), 1))(*[len(fs) for _, fs in terms])
         flat = [f for _, fs in terms for f in fs]
         self.factors = (ffi.SopFactor * max(len(flat), 1))(*[ffi.SopFactor(c, rot) for c, rot in flat])
-        self.scales = None if scales is None else np.ascontiguousarray(_wire(field, scales))
+        self.scales = None if scales is None else np.ascontiguousarray(fr.wire(field, scales))
         self.expr = ffi.SopExpression(self.ptrs, C.c_void_p(self.coeffs.ctypes.data), self.degrees, self.factors,
                                       None if self.scales is None else C.c_void_p(self.scales.ctypes.data), len(ptrs), len(terms),
                                       (0 if scales is None else len(scales)) if n_scales is None else n_scales, mode)
@@ -128,14 +85,7 @@ class Expression:
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in NAMES:
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    header, lib = assert_exported(NAMES)
     assert lib.panda_poly_sum_of_products.argtypes[3] is C.c_uint64 and lib.panda_poly_sum_of_products_plan.argtypes[0] is C.c_uint64
     for macro, value in (("MAX_COLUMNS", ffi.SOP_MAX_COLUMNS), ("MAX_TERMS", ffi.SOP_MAX_TERMS), ("MAX_FACTORS", ffi.SOP_MAX_FACTORS),
                          ("MAX_SCALES", ffi.SOP_MAX_SCALES), ("SCALE_NONE", ffi.SOP_SCALE_NONE), ("SCALE_PER_VECTOR", ffi.SOP_SCALE_PER_VECTOR),
@@ -232,10 +182,10 @@ def test_bad_arguments_are_refused_before_any_device_call():
         assert call(mode=mode, scales=[1] * (ffi.SOP_MAX_SCALES + 1)) == 1
     # constants at and above the modulus, per field
     for field in (0, 1, 2):
-        r = _modulus(field)
-        for bad in (r, r + 1, W - 1):
-            assert call(field=field, wire_coeffs=_words([bad])) == 1
-            assert call(field=field, terms=[(1, [(0, 0)]), (1, [(1, 0)])], wire_coeffs=_words([1, bad])) == 1
+        r = fr.modulus(field)
+        for bad in (r, r + 1, fr.W - 1):
+            assert call(field=field, wire_coeffs=fr.words([bad])) == 1
+            assert call(field=field, terms=[(1, [(0, 0)]), (1, [(1, 0)])], wire_coeffs=fr.words([1, bad])) == 1
 
             def bad_scale(e, bad=bad):
                 C.memmove(e.scales + 32, int(bad).to_bytes(32, "little"), 32)
@@ -257,47 +207,18 @@ def test_host_program_checks_the_bounds(tmp_path):
     """tests/host_check/poly_terms_host.cpp: the program builder and the per-element routine the kernel runs, on the host under FE29_CHECK,
     against 256-bit arithmetic of its own -- every operand p - 1, 64 terms of degree 4, one term of degree 256, coefficients 0 and p - 1,
     the three fields"""
-    exe = str(tmp_path / "poly_terms_host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-o", exe, os.path.join(HERE, "host_check", "poly_terms_host.cpp")], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert re.fullmatch(r"ok (\d+)\n", out.stdout) and int(out.stdout.split()[1]) >= 1000
+    assert run_host_check(tmp_path, "poly_terms_host.cpp") >= 1000
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
-class Harness:
-    """one device buffer per column and one for the output, each with a guard run behind the data"""
+class Harness(GuardedBuffers):
+    """one guarded device buffer per column and one for the output, of batch x n elements"""
 
     def __init__(self, gm, field, n, batch=1):
+        super().__init__()
         self.lib, self.field, self.n, self.batch = ffi.load(), field, n, batch
         self.bytes = batch * n * 32
         self.stream = gm.exec_stream.raw
-        self.bufs = []
-
-    def buffer(self, x=None, nbytes=None):
-        from gpu_util import DeviceBuffer
-        nbytes = self.bytes if nbytes is None else nbytes
-        d = DeviceBuffer(nbytes + GUARD_BYTES)
-        self.bufs.append(d)
-        ffi.check(self.lib.panda_memset(d.ptr, GUARD, nbytes + GUARD_BYTES), "memset")
-        if x is not None:
-            x = np.ascontiguousarray(x, np.uint32)
-            ffi.check(self.lib.panda_memcpy(d.ptr, C.c_void_p(x.ctypes.data), x.nbytes), "memcpy")
-        return d
-
-    def get(self, d, nbytes=None):
-        return d.to_host(np.uint32, nbytes=self.bytes if nbytes is None else nbytes)
-
-    def guard_ok(self, d, nbytes=None):
-        nbytes = self.bytes if nbytes is None else nbytes
-        return (d.to_host(np.uint8, nbytes=GUARD_BYTES, offset=nbytes) == GUARD).all()
 
     def call(self, ptrs, terms, out_ptr, scales=None, mode=0):
         x = Expression(self.field, ptrs, terms, scales, mode)
@@ -307,20 +228,14 @@ class Harness:
         """cols: (batch, n, 8) word arrays, one device buffer each -> the output words (batch, n, 8); in_place: the column d_out is.
         Checks the return code, the guards and that no input but the output changed."""
         ds = [self.buffer(c) for c in cols]
-        out = ds[in_place] if in_place is not None else self.buffer()
+        assert all(d.data_bytes == self.bytes for d in ds)
+        out = ds[in_place] if in_place is not None else self.buffer(nbytes=self.bytes)
         rc = self.call([d.ptr.value for d in ds], terms, out.ptr.value, scales, mode)
         assert rc == 0, rc
         for k, d in enumerate(ds):
-            assert self.guard_ok(d), "bytes behind the batch were written"
-            if k != in_place:
-                assert np.array_equal(self.get(d).reshape(cols[k].shape), cols[k]), "a column was written"
-        assert self.guard_ok(out)
+            assert self.guard_intact(d) if k == in_place else self.intact(d), "a column or the bytes behind the batch were written"
+        assert self.guard_intact(out)
         return self.get(out).reshape(self.batch, self.n, 8)
-
-    def close(self):
-        for d in self.bufs:
-            d.free()
-        self.bufs = []
 
 
 def _check(gm, field, cols, terms, scales=None, mode=0, in_place=None):
@@ -337,8 +252,8 @@ def _check(gm, field, cols, terms, scales=None, mode=0, in_place=None):
 
 
 def _gate_columns(field, seed, batch, n, planted=False):
-    r = _modulus(field)
-    cols = [_random(field, seed + k, batch, n, nonzero=(k == 3)) for k in range(8)]
+    r = fr.modulus(field)
+    cols = [fr.random_rows(field, seed + k, batch, n, nonzero=(k == 3)) for k in range(8)]
     if planted:  # c = -(q_L a + q_R b + q_M a b + q_C) / q_O
         ql, qr, qm, qo, qc, a, b, _ = cols
         cols[7] = [[-(ql[p][i] * a[p][i] + qr[p][i] * b[p][i] + qm[p][i] * a[p][i] * b[p][i] + qc[p][i]) * pow(qo[p][i], -1, r) % r for i in range(n)]
@@ -360,7 +275,7 @@ def test_gate_at_the_boundary_sizes(gm, batch):
 def test_rotations_wrap_inside_their_vector(gm):
     T = _tile()
     for n in (3, T + 1):
-        x = _random(0, 0x2A000 + n, 2, n)
+        x = fr.random_rows(0, 0x2A000 + n, 2, n)
         assert x[0] != x[1]
         xw = _col_words(0, x)
         for rot in (1, -1, n - 1, n, n + 1, -n, -(1 << 31)):
@@ -374,13 +289,13 @@ def test_rotations_wrap_inside_their_vector(gm):
 def test_the_grand_product_closes(gm):
     """Z from panda_poly_grand_product on a permuted multiset: Z[i+1] den[i] - Z[i] num[i] is zero at every i, at i = n - 1 because Z closes"""
     n = 3 * _tile() + 5
-    r = _modulus(0)
-    den = _random(0, 0x3A000, 1, n, nonzero=True)
+    r = fr.modulus(0)
+    den = fr.random_rows(0, 0x3A000, 1, n, nonzero=True)
     perm = np.random.default_rng(3).permutation(n)
     num = [[den[0][j] for j in perm]]
     zs, totals = pgm.panda_poly_gpu_grand_product(gm, [_col_words(0, num)[0]], [_col_words(0, den)[0]])
-    assert np.array_equal(totals[0], _wire(0, [1])[0])
-    z = [_plain(0, zs[0])]
+    assert np.array_equal(totals[0], fr.wire(0, [1])[0])
+    z = [fr.plain(0, zs[0])]
     got = _check(gm, 0, [z, den, num], [(1, [(0, 1), (1, 0)]), (r - 1, [(0, 0), (2, 0)])])
     assert not got.any()
 
@@ -388,11 +303,11 @@ def test_the_grand_product_closes(gm):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["fill", "copy", "coefficient_zero", "square", "all_minus_one_64x4", "degree_256", "columns_32"])
 def test_edge_expressions(gm, case):
-    n, batch, r = _tile() + 1, 2, _modulus(0)
-    x, y = _random(0, 0x4A000, batch, n), _random(0, 0x4B000, batch, n)
+    n, batch, r = _tile() + 1, 2, fr.modulus(0)
+    x, y = fr.random_rows(0, 0x4A000, batch, n), fr.random_rows(0, 0x4B000, batch, n)
     if case == "fill":
         got = _check(gm, 0, [x], [(12345, [])])
-        assert np.array_equal(got, np.broadcast_to(_wire(0, [12345])[0], (batch, n, 8)))
+        assert np.array_equal(got, np.broadcast_to(fr.wire(0, [12345])[0], (batch, n, 8)))
     elif case == "copy":
         got = _check(gm, 0, [x], [(1, [(0, 0)])])
         assert np.array_equal(got, _col_words(0, x))
@@ -406,48 +321,48 @@ def test_edge_expressions(gm, case):
     elif case == "all_minus_one_64x4":
         m1 = [[r - 1] * n for _ in range(batch)]
         got = _check(gm, 0, [m1, m1], [(r - 1, [(t & 1, t), (0, -t), (1, 0), (t & 1, 1)]) for t in range(64)], scales=[r - 1], mode=1)
-        assert np.array_equal(got, np.broadcast_to(_wire(0, [64])[0], (batch, n, 8))), "64 x (-1)^5, times -1"
+        assert np.array_equal(got, np.broadcast_to(fr.wire(0, [64])[0], (batch, n, 8))), "64 x (-1)^5, times -1"
     elif case == "degree_256":
         _check(gm, 0, [x, y], [(r - 1, [(f & 1, f - 128) for f in range(256)])])
     else:  # 32 column pointers, the cap: 31 into one buffer and one apart
         cols = [x] * 31 + [y]
         h = Harness(gm, 0, n, batch)
         try:
-            dx, dy, out = h.buffer(_col_words(0, x)), h.buffer(_col_words(0, y)), h.buffer()
+            dx, dy, out = h.buffer(_col_words(0, x)), h.buffer(_col_words(0, y)), h.buffer(nbytes=h.bytes)
             terms = [(c + 1, [(c, c)]) for c in range(32)]
             assert h.call([dx.ptr.value] * 31 + [dy.ptr.value], terms, out.ptr.value) == 0
-            assert np.array_equal(h.get(out).reshape(batch, n, 8), _expected(0, cols, terms)) and h.guard_ok(out)
+            assert np.array_equal(h.get(out).reshape(batch, n, 8), _expected(0, cols, terms)) and h.guard_intact(out)
         finally:
             h.close()
 
 
 @pytest.mark.gpu
 def test_columns_overlapping_by_half_a_vector(gm):
-    n, r = _tile() + 2, _modulus(0)
+    n, r = _tile() + 2, fr.modulus(0)
     half = n // 2
-    data = _random(0, 0x5A000, 1, n + half)[0]
+    data = fr.random_rows(0, 0x5A000, 1, n + half)[0]
     h = Harness(gm, 0, n, 1)
     try:
-        d = h.buffer(_wire(0, data), nbytes=(n + half) * 32)
-        out = h.buffer()
+        d = h.buffer(fr.wire(0, data))
+        out = h.buffer(nbytes=h.bytes)
         terms = [(1, [(0, 0), (1, 0)]), (r - 1, [(1, 1)]), (3, [(0, -1)])]
         assert h.call([d.ptr.value, d.ptr.value + half * 32], terms, out.ptr.value) == 0
         want = _expected(0, [[data[:n]], [data[half:half + n]]], terms)
         assert np.array_equal(h.get(out).reshape(1, n, 8), want)
-        assert h.guard_ok(out) and h.guard_ok(d, (n + half) * 32) and np.array_equal(h.get(d, (n + half) * 32).reshape(-1, 8), _wire(0, data))
+        assert h.guard_intact(out) and h.intact(d)
     finally:
         h.close()
 
 
 @pytest.mark.gpu
 def test_scales(gm):
-    T, r = _tile(), _modulus(0)
-    s = _random(0, 0x6A000, 1, 16)[0]
+    T, r = _tile(), fr.modulus(0)
+    s = fr.random_rows(0, 0x6A000, 1, 16)[0]
     terms = [(1, [(0, 0), (1, 0)]), (r - 1, [(2, 1)])]
-    cols = [_random(0, 0x6B000 + k, 5, T + 1) for k in range(3)]
+    cols = [fr.random_rows(0, 0x6B000 + k, 5, T + 1) for k in range(3)]
     _check(gm, 0, cols, terms, scales=s[:4], mode=1)  # PER_VECTOR, batch 5 over 4 scales: vector 4 takes scale 0
     for n in (3, T + 1):
-        cols = [_random(0, 0x6C000 + n + k, 2, n) for k in range(3)]
+        cols = [fr.random_rows(0, 0x6C000 + n + k, 2, n) for k in range(3)]
         _check(gm, 0, cols, terms, scales=s, mode=2)  # CYCLIC with 16 scales
         _check(gm, 0, cols, terms, scales=s[:5], mode=2)
         plain = _check(gm, 0, cols, terms)  # NONE with scales == NULL
@@ -460,13 +375,13 @@ def test_scales(gm):
 
 def _quotient_setup(log_n, log_blowup):
     """a, b random on H, c = a b; coefficients and the direct evaluation of (a b - c) / (X^n - 1) on the extended coset, all integers"""
-    r = _modulus(0)
+    r = fr.modulus(0)
     n, B = 1 << log_n, 1 << log_blowup
     N = n * B
-    w_N = _plain(0, po.root_of_unity(po.F_BN254_FR, log_n + log_blowup))[0]
+    w_N = fr.plain(0, po.root_of_unity(po.F_BN254_FR, log_n + log_blowup))[0]
     w_n, g = pow(w_N, B, r), 5
     assert pow(w_N, N, r) == 1 and pow(w_N, N // 2, r) != 1
-    ev_a, ev_b = _random(0, 0x7A000, 1, n)[0], _random(0, 0x7B000, 1, n)[0]
+    ev_a, ev_b = fr.random_rows(0, 0x7A000, 1, n)[0], fr.random_rows(0, 0x7B000, 1, n)[0]
     ev_c = [x * y % r for x, y in zip(ev_a, ev_b)]
     ninv = pow(n, -1, r)
     coeffs = [[ninv * sum(e[k] * pow(w_n, -j * k % n, r) for k in range(n)) % r for j in range(n)] for e in (ev_a, ev_b, ev_c)]
@@ -482,12 +397,12 @@ def test_a_real_quotient(gm, order):
     """evaluations on H -> inverse transform -> extension to the coset -> (a b - c) / Z_H by this call, against the direct O(n N) evaluation"""
     log_n, log_blowup = 5, 2
     r, n, B, N, w_N, w_n, g, evals, coeffs, quotient = _quotient_setup(log_n, log_blowup)
-    omega_n, omega_N, shift = _wire(0, [w_n])[0], _wire(0, [w_N])[0], _wire(0, [g])[0]
+    omega_n, omega_N, shift = fr.wire(0, [w_n])[0], fr.wire(0, [w_N])[0], fr.wire(0, [g])[0]
     cs = []
     for e, want in zip(evals, coeffs):
-        buf = np.array(_wire(0, e))
+        buf = np.array(fr.wire(0, e))
         pgm.panda_intt_bn254_gpu(gm, buf, omega_n, log_n)
-        assert np.array_equal(buf, _wire(0, want))
+        assert np.array_equal(buf, fr.wire(0, want))
         cs.append(buf)
     ext = pgm.panda_ntt_gpu_lde(gm, cs, omega_N, log_n, log_blowup, shift, field=0, order=order)
     zinv = [pow(pow(g, n, r) * pow(w_N, i * n, r) - 1, -1, r) for i in range(B)]  # 1 / Z_H on coset i
@@ -500,16 +415,16 @@ def test_a_real_quotient(gm, order):
         cols = [e.reshape(1, N, 8) for e in ext]
         want = quotient
         mode = ffi.SOP_SCALE_CYCLIC
-    got = pgm.panda_poly_gpu_sum_of_products(gm, cols, [(_wire(0, [k])[0], fs) for k, fs in terms], field=0, scales=_wire(0, zinv), scale_mode=mode)
-    assert np.array_equal(got.reshape(-1, 8), _wire(0, want))
+    got = pgm.panda_poly_gpu_sum_of_products(gm, cols, [(fr.wire(0, [k])[0], fs) for k, fs in terms], field=0, scales=fr.wire(0, zinv), scale_mode=mode)
+    assert np.array_equal(got.reshape(-1, 8), fr.wire(0, want))
 
 
 @pytest.mark.gpu
 def test_in_place_and_short_buffers(gm):
     from gpu_util import DeviceBuffer
-    T, r = _tile(), _modulus(0)
+    T, r = _tile(), fr.modulus(0)
     n, batch = 2 * T + 1, 2
-    cols = [_random(0, 0x8A000 + k, batch, n) for k in range(3)]
+    cols = [fr.random_rows(0, 0x8A000 + k, batch, n) for k in range(3)]
     words = [_col_words(0, c) for c in cols]
     for terms in ([(1, [(0, 0), (1, 1)]), (r - 1, [(2, -1), (0, 0)]), (5, [])],
                   [(1, [(0, n), (1, 1)]), (r - 1, [(2, -1), (0, -n)]), (5, [(0, 0), (0, 2 * n)])]):  # rotation n is rotation 0
@@ -522,15 +437,15 @@ def test_in_place_and_short_buffers(gm):
     h = Harness(gm, 0, n, batch)
     short = DeviceBuffer(h.bytes - 32)  # one element short
     try:
-        a, b, out = h.buffer(words[0]), h.buffer(words[1]), h.buffer()
+        a, b, out = h.buffer(words[0]), h.buffer(words[1]), h.buffer(nbytes=h.bytes)
         ffi.check(h.lib.panda_memset(short.ptr, GUARD, h.bytes - 32), "memset")
         terms = [(1, [(0, 0), (1, 0)])]
         assert h.call([a.ptr.value, b.ptr.value], terms, a.ptr.value + 32) == 1 and h.call([a.ptr.value, b.ptr.value], [(1, [(0, 1)])], a.ptr.value) == 1
         assert h.call([short.ptr.value, b.ptr.value], terms, out.ptr.value) == 1 and h.call([a.ptr.value, short.ptr.value], terms, out.ptr.value) == 1
         assert h.call([a.ptr.value, b.ptr.value], terms, short.ptr.value) == 1 and h.call([short.ptr.value], [(1, [(0, 0)])], short.ptr.value) == 1
         assert h.call([a.ptr.value, b.ptr.value, short.ptr.value], terms, out.ptr.value) == 1, "a short column no factor names"
-        assert (short.to_host(np.uint8) == GUARD).all() and (out.to_host(np.uint8) == GUARD).all(), "a refused call wrote to a buffer"
-        assert np.array_equal(h.get(a).reshape(words[0].shape), words[0]) and np.array_equal(h.get(b).reshape(words[1].shape), words[1])
+        assert (short.to_host(np.uint8) == GUARD).all() and h.untouched(out), "a refused call wrote to a buffer"
+        assert h.intact(a) and h.intact(b)
         assert h.call([a.ptr.value, b.ptr.value], terms, out.ptr.value) == 0
         assert np.array_equal(h.get(out).reshape(batch, n, 8), _expected(0, cols[:2], terms))
     finally:
@@ -541,55 +456,49 @@ def test_in_place_and_short_buffers(gm):
 @pytest.mark.gpu
 @pytest.mark.parametrize("field", [1, 2])
 def test_other_fields(gm, field):
-    n, r = _tile() + 1, _modulus(field)
+    n, r = _tile() + 1, fr.modulus(field)
     _check(gm, field, _gate_columns(field, 0x9A000 + field, 2, n), GATE + [(r - 1, [(7, 1), (5, -1)])], scales=[r - 1, 2, 3], mode=2)
     assert not _check(gm, field, _gate_columns(field, 0x9B000 + field, 2, n, planted=True), GATE).any()
-
-
-def _free_bytes(lib):
-    free, total = C.c_size_t(0), C.c_size_t(0)
-    ffi.check(lib.panda_mem_get_info(C.byref(free), C.byref(total)), "mem_info")
-    return free.value
 
 
 @pytest.mark.gpu
 def test_scratch_is_reused_and_released(gm):
     n, batch = 5 * _tile() - 7, 4
-    cols = [_col_words(0, _random(0, 0xAA000 + k, batch, n)) for k in range(2)]
+    cols = [_col_words(0, fr.random_rows(0, 0xAA000 + k, batch, n)) for k in range(2)]
     terms = [(1, [(0, 0), (1, 1)])]
     h = Harness(gm, 0, n, batch)
     try:
-        a, b, out = h.buffer(cols[0]), h.buffer(cols[1]), h.buffer()
+        a, b, out = h.buffer(cols[0]), h.buffer(cols[1]), h.buffer(nbytes=h.bytes)
         run = lambda: h.call([a.ptr.value, b.ptr.value], terms, out.ptr.value)
         assert run() == 0  # whatever the runtime keeps from a kernel's first launch is there before the baseline is read
         ffi.check(h.lib.panda_ntt_tear_down(), "tear_down")
-        before = _free_bytes(h.lib)
+        before = free_bytes(h.lib)
         assert run() == 0
-        first = _free_bytes(h.lib)
+        first = free_bytes(h.lib)
         o1 = h.get(out)
         assert run() == 0
-        assert _free_bytes(h.lib) == first, "a repeated identical call allocated"
+        assert free_bytes(h.lib) == first, "a repeated identical call allocated"
         assert np.array_equal(h.get(out), o1)
         ffi.check(h.lib.panda_ntt_tear_down(), "tear_down")
-        assert _free_bytes(h.lib) == before, "panda_ntt_tear_down releases the scratch"
+        assert free_bytes(h.lib) == before, "panda_ntt_tear_down releases the scratch"
     finally:
         h.close()
 
 
 @pytest.mark.gpu
 def test_gpu_manager_helper(gm):
-    n, batch, r = _tile() + 3, 3, _modulus(0)
-    cols = [_random(0, 0xBA000 + k, batch, n) for k in range(3)]
+    n, batch, r = _tile() + 3, 3, fr.modulus(0)
+    cols = [fr.random_rows(0, 0xBA000 + k, batch, n) for k in range(3)]
     words = [np.array(_col_words(0, c)) for c in cols]
     keep = [w.copy() for w in words]
     terms = [(1, [(0, 0), (1, 0)]), (r - 1, [(2, 1)]), (9, [])]
-    wire_terms = [(_wire(0, [k])[0], fs) for k, fs in terms]
+    wire_terms = [(fr.wire(0, [k])[0], fs) for k, fs in terms]
     got = pgm.panda_poly_gpu_sum_of_products(gm, words, wire_terms)
     assert got.shape == (batch, n, 8) and got.dtype == np.uint32 and np.array_equal(got, _expected(0, cols, terms))
     s = [3, r - 1]
-    got = pgm.panda_poly_gpu_sum_of_products(gm, words, wire_terms, scales=_wire(0, s), scale_mode=ffi.SOP_SCALE_PER_VECTOR)
+    got = pgm.panda_poly_gpu_sum_of_products(gm, words, wire_terms, scales=fr.wire(0, s), scale_mode=ffi.SOP_SCALE_PER_VECTOR)
     assert np.array_equal(got, _expected(0, cols, terms, s, 1))
-    got = pgm.panda_poly_gpu_sum_of_products(gm, [w[0] for w in words], wire_terms, scales=_wire(0, s), scale_mode=ffi.SOP_SCALE_CYCLIC)
+    got = pgm.panda_poly_gpu_sum_of_products(gm, [w[0] for w in words], wire_terms, scales=fr.wire(0, s), scale_mode=ffi.SOP_SCALE_CYCLIC)
     assert got.shape == (n, 8) and np.array_equal(got, _expected(0, [c[:1] for c in cols], terms, s, 2)[0])
     assert all(np.array_equal(w, k) for w, k in zip(words, keep)), "the helper changed its input"
     with pytest.raises(pgm.PandaGpuError):
@@ -603,7 +512,7 @@ def test_gpu_manager_helper(gm):
 def test_2_24(gm):
     """a[i] b[i+1] - c[i-1] at 2^24 on generated data, sampled indices against integers"""
     from gpu_util import NULL_STREAM, DeviceBuffer
-    lib, n, r = ffi.load(), 1 << 24, _modulus(0)
+    lib, n, r = ffi.load(), 1 << 24, fr.modulus(0)
     bufs = [DeviceBuffer(n * 32) for _ in range(4)]
     try:
         for k in range(3):
@@ -612,7 +521,7 @@ def test_2_24(gm):
         terms = [(1, [(0, 0), (1, 1)]), (r - 1, [(2, -1)])]
         x = Expression(0, [b.ptr.value for b in bufs[:3]], terms)
         assert lib.panda_poly_sum_of_products(0, C.byref(x.expr), bufs[3].ptr, n, 1, gm.exec_stream.raw) == 0
-        elem = lambda b, i: _plain(0, b.to_host(np.uint32, nbytes=32, offset=(i % n) * 32))[0]
+        elem = lambda b, i: fr.plain(0, b.to_host(np.uint32, nbytes=32, offset=(i % n) * 32))[0]
         for i in [0, 1, n - 1, n - 2, _tile() - 1, _tile()] + [int(v) for v in np.random.default_rng(24).integers(0, n, 58)]:
             assert elem(bufs[3], i) == (elem(bufs[0], i) * elem(bufs[1], i + 1) - elem(bufs[2], i - 1)) % r, i
     finally:

@@ -9,22 +9,16 @@ buffer carries a guard run of a fixed byte pattern behind the data, which no cal
 passes an invalid structure to the product: that is tests/host_check/sparse_host.cpp's ground."""
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import oracle as po
-import pyref
+import field_ref as fr
+from gpu_util import GuardedBuffers, assert_exported, gm, run_host_check  # noqa: F401
 from panda_amd import gpu_ffi as ffi
 from panda_amd import gpu_manager as pgm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-GUARD, GUARD_BYTES = 0xA5, 4096
-W = 1 << 256
 CAP = 1 << 28
 NAMES = ("panda_sparse_matvec", "panda_sparse_check", "panda_sparse_plan")
 NO_INDEX = (1 << 64) - 1
@@ -41,26 +35,6 @@ def _tile():
     rc, tile, chunk, _, _ = _plan(ffi.load(), 8, 8, 8, 1)
     assert rc == 0 and tile >= 2 and chunk >= 1
     return tile, chunk
-
-
-@functools.lru_cache(maxsize=None)
-def _modulus(field):
-    return pyref.limbs_to_int(po.field_info(po.FR_OF[field])["p"])
-
-
-def _words(vals):
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), np.uint32).reshape(-1, 8)
-
-
-def _wire(field, vals):
-    r = _modulus(field)
-    return _words([v % r * W % r for v in vals])
-
-
-def _random(field, seed, n):
-    r = _modulus(field)
-    raw = np.random.default_rng(seed).bytes(40 * n)
-    return [int.from_bytes(raw[40 * j:40 * j + 40], "little") % r for j in range(n)]
 
 
 def _row_ptr(lengths):
@@ -80,20 +54,13 @@ def _random_lengths(seed, nnz, longest=6):
 
 def _product(field, row_ptr, col, vals, z):
     """the definition, on plain residues"""
-    p = _modulus(field)
+    p = fr.modulus(field)
     return [sum(vals[k] * z[col[k]] for k in range(int(row_ptr[r]), int(row_ptr[r + 1]))) % p for r in range(len(row_ptr) - 1)]
 
 
 # ------------------------------------------------------------------------------------------------- without a GPU
 def test_symbols_in_header_ffi_and_library():
-    header = open(os.path.join(ROOT, "include", "panda_interface.h")).read()
-    exported = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    lib = ffi.load()
-    for name in NAMES:
-        assert re.search(r"panda_error\s+%s\s*\(" % name, header)
-        assert name in ffi.ADDITIVE_SYMBOLS and name in ffi.ALL_SYMBOLS
-        assert re.search(r"\sT\s+%s$" % name, exported, re.M)
-        assert getattr(lib, name).argtypes is not None
+    header, _ = assert_exported(NAMES)
     assert re.search(r"typedef\s+struct\s+panda_csr_matrix", header)
     assert [f[0] for f in ffi.CsrMatrix._fields_] == ["d_row_ptr", "d_col", "d_values", "n_rows", "n_cols", "nnz"]
     assert C.sizeof(ffi.CsrMatrix) == 48 and ffi.CsrMatrix.n_rows.offset == 24 and ffi.CsrMatrix.nnz.offset == 40
@@ -178,47 +145,16 @@ def test_host_program_checks_the_bounds_and_the_accesses(tmp_path):
     FE29_CHECK against 256-bit arithmetic of its own, for the three fields: every value and z p - 1, rows of length 1, 2, 3 and 4 T + 1,
     and -- through an index-checking accessor -- row_ptr all ones, decreasing and random, col all ones and random: no access leaves its
     extent"""
-    exe = str(tmp_path / "sparse_host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-o", exe, os.path.join(HERE, "host_check", "sparse_host.cpp")], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    assert re.fullmatch(r"ok (\d+)\n", out.stdout) and int(out.stdout.split()[1]) >= 1000
+    assert run_host_check(tmp_path, "sparse_host.cpp") >= 1000
 
 
 # ------------------------------------------------------------------------------------------------- on the device
-@pytest.fixture(scope="module")
-def gm():
-    m = pgm.PandaGpuManager(0)
-    yield m
-    m.deinit()
-
-
-class Dev:
-    """device buffers with a guard run behind the data, and the calls over them"""
+class Dev(GuardedBuffers):
+    """guarded device buffers, and the calls over them"""
 
     def __init__(self, gm, field=0):
-        self.lib, self.field, self.stream, self.bufs = ffi.load(), field, gm.exec_stream.raw, []
-
-    def buffer(self, x=None, nbytes=None):
-        from gpu_util import DeviceBuffer
-        if x is not None:
-            x = np.ascontiguousarray(x, np.uint32)
-            nbytes = x.nbytes
-        d = DeviceBuffer(nbytes + GUARD_BYTES)
-        d.data_bytes, d.host = nbytes, x
-        self.bufs.append(d)
-        ffi.check(self.lib.panda_memset(d.ptr, GUARD, nbytes + GUARD_BYTES), "memset")
-        if x is not None and nbytes:
-            ffi.check(self.lib.panda_memcpy(d.ptr, C.c_void_p(x.ctypes.data), nbytes), "memcpy")
-        return d
-
-    def get(self, d):
-        return d.to_host(np.uint32, nbytes=d.data_bytes)
-
-    def intact(self, d):
-        """the guard behind the data, and the data itself if the buffer was an input"""
-        guard = (d.to_host(np.uint8, nbytes=GUARD_BYTES, offset=d.data_bytes) == GUARD).all()
-        return guard and (d.host is None or d.data_bytes == 0 or np.array_equal(self.get(d), d.host.reshape(-1)))
+        super().__init__()
+        self.lib, self.field, self.stream = ffi.load(), field, gm.exec_stream.raw
 
     def matrix(self, row_ptr, col, value_words, n_cols):
         """-> (ffi.CsrMatrix, its three buffers); an empty col / values array is passed as NULL"""
@@ -235,11 +171,6 @@ class Dev:
     def matvec(self, m, z, out, batch=1):
         return self.lib.panda_sparse_matvec(self.field, C.byref(m), z.ptr, out.ptr, batch, self.stream)
 
-    def close(self):
-        for d in self.bufs:
-            d.free()
-        self.bufs = []
-
 
 def _run(gm, field, row_ptr, col, vals, zs, n_cols, what=""):
     """check + product of a valid matrix on plain residues against the definition, for the vectors `zs` in one batched call; returns the
@@ -249,14 +180,14 @@ def _run(gm, field, row_ptr, col, vals, zs, n_cols, what=""):
     assert int(row_ptr[-1]) == len(col) == len(vals) and all(len(z) == n_cols for z in zs)
     h = Dev(gm, field)
     try:
-        m, bufs = h.matrix(row_ptr, col, _wire(field, vals) if len(vals) else np.zeros((0, 8), np.uint32), n_cols)
-        z = h.buffer(np.concatenate([_wire(field, z) for z in zs]))
+        m, bufs = h.matrix(row_ptr, col, fr.wire(field, vals) if len(vals) else np.zeros((0, 8), np.uint32), n_cols)
+        z = h.buffer(np.concatenate([fr.wire(field, z) for z in zs]))
         out = h.buffer(nbytes=batch * n_rows * 32)
         assert h.check(m) == (0, NO_INDEX), what
         assert h.matvec(m, z, out, batch) == 0, what
         got = h.get(out).reshape(batch, n_rows, 8)
         for p in range(batch):
-            want = _wire(field, _product(field, row_ptr, col, vals, zs[p]))
+            want = fr.wire(field, _product(field, row_ptr, col, vals, zs[p]))
             bad = np.nonzero((got[p] != want).any(axis=1))[0]
             assert bad.size == 0, (what, field, "vector", p, "rows", bad[:8].tolist(), "of", n_rows, "nnz", len(col))
         for d in bufs + (z, out):
@@ -270,7 +201,7 @@ def _random_matrix(seed, lengths, n_cols, field=0):
     row_ptr = _row_ptr(lengths)
     nnz = int(row_ptr[-1])
     col = np.random.default_rng(seed).integers(0, n_cols, nnz).astype(np.uint32)
-    return row_ptr, col, _random(field, seed + 1, nnz), _random(field, seed + 2, n_cols)
+    return row_ptr, col, fr.random_residues(field, seed + 1, nnz), fr.random_residues(field, seed + 2, n_cols)
 
 
 @pytest.mark.gpu
@@ -320,18 +251,18 @@ def test_columns(gm):
     # one column: every gather hits one element
     lengths = _random_lengths(0x2E001, T + 9)
     row_ptr = _row_ptr(lengths)
-    _run(gm, 0, row_ptr, np.zeros(T + 9, np.uint32), _random(0, 0x2E002, T + 9), [_random(0, 0x2E003, 1)], 1, "n_cols 1")
+    _run(gm, 0, row_ptr, np.zeros(T + 9, np.uint32), fr.random_residues(0, 0x2E002, T + 9), [fr.random_residues(0, 0x2E003, 1)], 1, "n_cols 1")
     # a row that names one column five times; unsorted columns inside the rows
     row_ptr = _row_ptr([5, 4, 6, 1])
     col = np.array([3, 3, 3, 3, 3, 9, 0, 7, 2, 8, 8, 1, 0, 9, 4, 5], np.uint32)
-    _run(gm, 0, row_ptr, col, _random(0, 0x2E004, 16), [_random(0, 0x2E005, 10)], 10, "repeats and unsorted columns")
+    _run(gm, 0, row_ptr, col, fr.random_residues(0, 0x2E004, 16), [fr.random_residues(0, 0x2E005, 10)], 10, "repeats and unsorted columns")
 
 
 @pytest.mark.gpu
 def test_extreme_operands(gm):
     T, _ = _tile()
     for field in (0, 1, 2):
-        p = _modulus(field)
+        p = fr.modulus(field)
         lengths = [1, 2, 3, 4, 5, 6, 7, 0, 8] + _random_lengths(0x2F000 + field, T + 1 - 36)
         row_ptr, col, _, _ = _random_matrix(0x2F100 + field, lengths, 19, field)
         nnz = int(row_ptr[-1])
@@ -340,7 +271,7 @@ def test_extreme_operands(gm):
         vals = [(0, 1, p - 1)[k % 3] for k in range(nnz)]
         z = [0 if c % 4 == 1 else p - 1 if c % 4 == 2 else c + 1 for c in range(19)]
         _run(gm, field, row_ptr, col, vals, [z], 19, "0, 1, p - 1 and zeros in z")
-        _run(gm, field, row_ptr, col, _random(field, 0x2F200 + field, nnz), [_random(field, 0x2F300 + field, 19)], 19, "random, field %d" % field)
+        _run(gm, field, row_ptr, col, fr.random_residues(field, 0x2F200 + field, nnz), [fr.random_residues(field, 0x2F300 + field, 19)], 19, "random, field %d" % field)
 
 
 @pytest.mark.gpu
@@ -349,7 +280,7 @@ def test_batch_equals_single_calls(gm):
     lengths = _random_lengths(0x30001, 2 * T + 77, longest=40)
     n_cols = len(lengths) + 13  # n_rows != n_cols
     row_ptr, col, vals, _ = _random_matrix(0x30002, lengths, n_cols)
-    zs = [_random(0, 0x30010 + p, n_cols) for p in range(3)]
+    zs = [fr.random_residues(0, 0x30010 + p, n_cols) for p in range(3)]
     together = _run(gm, 0, row_ptr, col, vals, zs, n_cols, "batch 3")
     for p in range(3):
         alone = _run(gm, 0, row_ptr, col, vals, [zs[p]], n_cols, "single %d" % p)
@@ -364,12 +295,12 @@ def test_two_runs_give_equal_bytes_and_short_buffers_are_refused(gm):
     n_rows = len(row_ptr) - 1
     h = Dev(gm, 0)
     try:
-        m, _ = h.matrix(row_ptr, col, _wire(0, vals), 101)
-        zb = h.buffer(_wire(0, z))
+        m, _ = h.matrix(row_ptr, col, fr.wire(0, vals), 101)
+        zb = h.buffer(fr.wire(0, z))
         a, b = h.buffer(nbytes=n_rows * 32), h.buffer(nbytes=n_rows * 32)
         assert h.matvec(m, zb, a) == 0 and h.matvec(m, zb, b) == 0 and h.matvec(m, zb, a) == 0
         assert np.array_equal(h.get(a), h.get(b)) and h.intact(a) and h.intact(b)
-        assert np.array_equal(h.get(a).reshape(-1, 8), _wire(0, _product(0, row_ptr, col, vals, z)))
+        assert np.array_equal(h.get(a).reshape(-1, 8), fr.wire(0, _product(0, row_ptr, col, vals, z)))
         # buffers of the library's allocator that are shorter than stated: refused, nothing written
         before = h.get(a).copy()
         wide = ffi.CsrMatrix(m.d_row_ptr, m.d_col, m.d_values, m.n_rows + 2000, m.n_cols, m.nnz)  # row_ptr and out too short
@@ -389,12 +320,12 @@ def test_two_runs_give_equal_bytes_and_short_buffers_are_refused(gm):
 def test_check_reports_the_first_defect(gm):
     T, _ = _tile()
     field = 0
-    p = _modulus(field)
+    p = fr.modulus(field)
     lengths = _random_lengths(0x32001, 2 * T + 5)
     n_cols = 40
     row_ptr, col, vals, _ = _random_matrix(0x32002, lengths, n_cols)
     nnz, n_rows = len(col), len(row_ptr) - 1
-    words = _wire(field, vals)
+    words = fr.wire(field, vals)
     r1, r2 = n_rows // 3, n_rows - 4          # rows whose row_ptr gets raised above the next one
     k1, k2 = T // 2 + 3, T + 17               # nonzeros in two different tiles
 
@@ -426,7 +357,7 @@ def test_check_reports_the_first_defect(gm):
 
     def values(*ks, value=p):
         vw = words.copy()
-        vw[list(ks)] = _words([value])[0]
+        vw[list(ks)] = fr.words([value])[0]
         return vw
 
     assert report() == (0, NO_INDEX)
@@ -440,7 +371,7 @@ def test_check_reports_the_first_defect(gm):
     assert report(rp=last) == (3, NO_INDEX)
     assert report(cl=columns(k2)) == (4, k2) and report(cl=columns(k1, k2)) == (4, k1) and report(cl=columns(k1, value=0xFFFFFFFF)) == (4, k1)
     assert report(cl=columns(nnz - 1, value=n_cols - 1)) == (0, NO_INDEX), "the largest legal column"
-    assert report(vw=values(k2)) == (5, k2) and report(vw=values(k2, k1)) == (5, k1) and report(vw=values(k1, value=W - 1)) == (5, k1)
+    assert report(vw=values(k2)) == (5, k2) and report(vw=values(k2, k1)) == (5, k1) and report(vw=values(k1, value=fr.W - 1)) == (5, k1)
     assert report(vw=values(k1, value=p - 1)) == (0, NO_INDEX), "the largest legal value"
     assert report(rp=raised(r2), vw=values(k1)) == (2, r2), "the smaller class wins, whatever the indices"
     assert report(rp=raised(r2), cl=columns(0), vw=values(0)) == (2, r2)
@@ -448,10 +379,10 @@ def test_check_reports_the_first_defect(gm):
     assert report(rp=first, vw=values(k1), only="where") == NO_INDEX
     # the Python helper raises on a defect and multiplies otherwise
     with pytest.raises(pgm.PandaGpuError, match="SparseDefect4"):
-        pgm.panda_sparse_gpu_matvec(gm, row_ptr, columns(k1), words, _wire(field, range(n_cols)), n_cols, field)
-    z = _random(field, 0x32003, n_cols)
-    got = pgm.panda_sparse_gpu_matvec(gm, row_ptr, col, words, _wire(field, z), n_cols, field)
-    assert np.array_equal(got, _wire(field, _product(field, row_ptr, col, vals, z)))
+        pgm.panda_sparse_gpu_matvec(gm, row_ptr, columns(k1), words, fr.wire(field, range(n_cols)), n_cols, field)
+    z = fr.random_residues(field, 0x32003, n_cols)
+    got = pgm.panda_sparse_gpu_matvec(gm, row_ptr, col, words, fr.wire(field, z), n_cols, field)
+    assert np.array_equal(got, fr.wire(field, _product(field, row_ptr, col, vals, z)))
 
 
 @pytest.mark.gpu
@@ -460,7 +391,7 @@ def test_r1cs_composes_with_the_sum_of_products(gm):
     a b - c by panda_poly_sum_of_products on the device-resident results: zero for a satisfying witness, non-zero exactly at the rows that
     read a corrupted entry"""
     field, n = 0, 300
-    p = _modulus(field)
+    p = fr.modulus(field)
     X, Y, Wv, OUT = (lambda i, b=b: 1 + b * n + i for b in range(4))
     n_cols, n_rows = 1 + 4 * n, 3 * n
     rows = {"A": [], "B": [], "C": []}
@@ -468,7 +399,7 @@ def test_r1cs_composes_with_the_sum_of_products(gm):
         rows["A"] += [[(X(i), 1)], [(Y(i), 1)], [(Wv(i), 1), (0, 5), (X(i), 1)]]  # unsorted columns in the third row
         rows["B"] += [[(X(i), 1)], [(X(i), 1)], [(0, 1)]]
         rows["C"] += [[(Y(i), 1)], [(Wv(i), 1)], [(OUT(i), 1)]]
-    xs = _random(field, 0x33001, n)
+    xs = fr.random_residues(field, 0x33001, n)
     good = [1] + xs + [x * x % p for x in xs] + [x * x * x % p for x in xs] + [(x * x * x + x + 5) % p for x in xs]
     j = 123
     bad = list(good)
@@ -477,18 +408,18 @@ def test_r1cs_composes_with_the_sum_of_products(gm):
     assert 5 * n > T, "A crosses a tile end"
     h = Dev(gm, field)
     try:
-        z = h.buffer(np.concatenate([_wire(field, good), _wire(field, bad)]))
+        z = h.buffer(np.concatenate([fr.wire(field, good), fr.wire(field, bad)]))
         outs = []
         for name in "ABC":
             lengths = [len(r) for r in rows[name]]
             flat = [e for r in rows[name] for e in r]
-            m, _ = h.matrix(_row_ptr(lengths), [c for c, _ in flat], _wire(field, [v for _, v in flat]), n_cols)
+            m, _ = h.matrix(_row_ptr(lengths), [c for c, _ in flat], fr.wire(field, [v for _, v in flat]), n_cols)
             assert h.check(m) == (0, NO_INDEX)
             out = h.buffer(nbytes=2 * n_rows * 32)
             assert h.matvec(m, z, out, batch=2) == 0
             outs.append(out)
         ptrs = (C.c_void_p * 3)(*[o.ptr.value for o in outs])
-        coeffs = _wire(field, [1, p - 1])
+        coeffs = fr.wire(field, [1, p - 1])
         degrees = (C.c_uint * 2)(2, 1)
         factors = (ffi.SopFactor * 3)(ffi.SopFactor(0, 0), ffi.SopFactor(1, 0), ffi.SopFactor(2, 0))
         expr = ffi.SopExpression(ptrs, C.c_void_p(coeffs.ctypes.data), degrees, factors, None, 3, 2, 0, ffi.SOP_SCALE_NONE)
@@ -498,7 +429,7 @@ def test_r1cs_composes_with_the_sum_of_products(gm):
         assert not got[0].any(), "a satisfying witness leaves a b - c zero in every row"
         assert np.nonzero(got[1].any(axis=1))[0].tolist() == [3 * j, 3 * j + 1], "the rows that read y_j"
         az = h.get(outs[0]).reshape(2, n_rows, 8)[0]
-        assert np.array_equal(az[2::3], _wire(field, [(x * x * x + x + 5) % p for x in xs]))
+        assert np.array_equal(az[2::3], fr.wire(field, [(x * x * x + x + 5) % p for x in xs]))
         assert all(h.intact(d) for d in h.bufs)
     finally:
         h.close()
