@@ -925,6 +925,17 @@ panda_error panda_debug_fe_internal(unsigned field_id, unsigned op, void *d_r, c
  * the width of r per element; d_a or d_b may be NULL where the op takes none.  panda_error_invalid_value, with nothing launched, for a
  * bad curve or a (curve, op) pair outside the table.  Device pointers. */
 panda_error panda_debug_xyzz_internal(unsigned curve, unsigned op, void *d_r, const void *d_a, const void *d_b, size_t n, panda_stream stream);
+/* Sets the scratch the entry points reuse between calls, so that a test can run a call on memory of its choosing: synchronises the
+ * device, overwrites the WHOLE capacity of the calling thread's scratch arena on the current device and, if it has been allocated, the
+ * calling thread's pinned mailbox, synchronises again, and reports the arena's base and capacity (either pointer may be NULL).
+ *   mode 0: every byte becomes value & 0xFF.
+ *   mode 1: 32-bit word i (i = 0, 1, ... from the base, taken modulo 2^32; the mailbox's words count from 0 again) becomes h(i ^ value),
+ *           h(x): x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16  in 32-bit arithmetic (a bijection).  The one
+ *           to three bytes behind the arena's last whole word become value & 0xFF.
+ * It allocates neither an arena nor a mailbox: with no arena it reports *base = NULL, *capacity = 0, and with neither it makes no
+ * runtime call at all.  panda_error_invalid_value, with nothing written (*base and *capacity included), for any other mode.  What a
+ * later call reserves beyond the capacity reported here is a fresh allocation, which this call did not fill. */
+panda_error panda_debug_scratch_fill(unsigned mode, unsigned value, void **base, size_t *capacity);
 
 const char *panda_version(void);
 

@@ -218,6 +218,54 @@ void clock_delta_out(const ClockDelta &d, uint64_t *out)
 ClockDelta &thread_msm_clock() { return g_msm_clock; }
 ClockDelta &thread_ntt_clock() { return g_ntt_clock; }
 
+namespace {
+// panda_debug_scratch_fill, mode 1: the "lowbias32" mix, a bijection of the 32-bit words (xor-shifts and odd multipliers)
+__host__ __device__ inline uint32_t scratch_hash(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    return x ^ (x >> 16);
+}
+
+// words [0, words) of an arena: four at a time where a whole uint4 fits, the last one to three one by one
+__global__ void __launch_bounds__(256) k_scratch_hash_fill(uint32_t *__restrict__ base, size_t words, uint32_t seed)
+{
+    const size_t quads = words / 4;
+    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (size_t)gridDim.x * 256) {
+        const uint32_t i = (uint32_t)(4 * q);
+        reinterpret_cast<uint4 *>(base)[q] = make_uint4(scratch_hash(i ^ seed), scratch_hash((i + 1) ^ seed), scratch_hash((i + 2) ^ seed), scratch_hash((i + 3) ^ seed));
+    }
+    if (blockIdx.x == 0 && 4 * quads + threadIdx.x < words) base[4 * quads + threadIdx.x] = scratch_hash((uint32_t)(4 * quads + threadIdx.x) ^ seed);
+}
+} // namespace
+
+// panda_debug_scratch_fill (include/panda_interface.h): the calling thread's arena on the current device and its mailbox, whole
+static hipError_t debug_scratch_fill(unsigned mode, unsigned value, void **base, size_t *capacity)
+{
+    if (mode > 1) return hipErrorInvalidValue;
+    Arena &arena = thread_arena();
+    int dev = -1;
+    const bool have_arena = arena.base && hipGetDevice(&dev) == hipSuccess && dev == arena.device;
+    if (base) *base = have_arena ? arena.base : nullptr;
+    if (capacity) *capacity = have_arena ? arena.capacity : 0;
+    if (!have_arena && !g_mailbox.words) return hipSuccess; // nothing to fill, and no runtime call: a machine without a device answers too
+    PANDA_TRY(hipDeviceSynchronize());
+    if (have_arena) {
+        const size_t words = arena.capacity / 4;
+        if (mode == 0 || arena.capacity % 4) PANDA_TRY(hipMemsetAsync(arena.base, (int)(value & 0xFFu), arena.capacity, nullptr));
+        if (mode == 1 && words) {
+            const unsigned blocks = (unsigned)std::min<size_t>((words / 4 + 255) / 256 + 1, 16384);
+            hipLaunchKernelGGL(k_scratch_hash_fill, dim3(blocks), dim3(256), 0, nullptr, (uint32_t *)arena.base, words, (uint32_t)value);
+            PANDA_TRY(hipGetLastError());
+        }
+    }
+    if (g_mailbox.words) // pinned host memory, and the device is idle: the host writes it
+        for (size_t i = 0; i < MAILBOX_WORDS; i++) g_mailbox.words[i] = mode == 0 ? (value & 0xFFu) * 0x01010101u : scratch_hash((uint32_t)i ^ (uint32_t)value);
+    return hipDeviceSynchronize();
+}
+
 hipError_t release_thread_arena()
 {
     g_helper.drop();
@@ -807,6 +855,12 @@ panda_error panda_clock_delta(const void *before, const void *after, uint64_t *o
     if (!before || !after || !out) return panda_error_invalid_value;
     panda::clock_delta_out(panda::clock_delta((const uint64_t *)before, (const uint64_t *)after), out);
     return panda_success;
+}
+
+panda_error panda_debug_scratch_fill(unsigned mode, unsigned value, void **base, size_t *capacity)
+{
+    const hipError_t e = panda::debug_scratch_fill(mode, value, base, capacity);
+    return e == hipErrorInvalidValue ? panda_error_invalid_value : static_cast<panda_error>(e);
 }
 
 const char *panda_msm_phase_name(unsigned phase) { return phase < PANDA_MSM_PHASES ? kPhaseNames[phase] : ""; }

@@ -116,7 +116,7 @@ ADDITIVE_SYMBOLS = [
     "panda_msm_last_phase_ms", "panda_msm_phase_name", "panda_ntt_last_device_ms", "panda_ntt_pass_plan", "panda_ntt_set_streamed_tables", "panda_ntt_execute_bn254_inverse", "panda_ntt_execute_bls12_377_v1", "panda_ntt_execute_bls12_377_inverse", "panda_msm_combine_bn254",
     "panda_msm_combine_bls12_377", "panda_msm_setup_bn254_g2", "panda_msm_execute_bn254_g2", "panda_msm_execute_bn254_g2_host", "panda_msm_combine_bn254_g2", "panda_msm_setup_bls12_381", "panda_msm_execute_bls12_381", "panda_msm_execute_bls12_381_host", "panda_msm_combine_bls12_381",
     "panda_ntt_execute_bls12_381_v1", "panda_ntt_execute_bls12_381_inverse", "panda_ntt_execute_bn254_coset", "panda_ntt_execute_bn254_coset_inverse", "panda_ntt_execute_bn254_bitrev_out", "panda_ntt_execute_bn254_inverse_bitrev_in", "panda_ntt_slab_step1_bn254", "panda_ntt_slab_step2_bn254", "panda_ntt_slab_step1_bn254_enqueue", "panda_ntt_slab_step2_bn254_enqueue", "panda_ntt_slab_inverse_step1_bn254_enqueue", "panda_ntt_slab_inverse_step2_bn254_enqueue", "panda_gen_scalars", "panda_gen_bases",
-    "panda_debug_field_op", "panda_debug_curve_op", "panda_debug_fe_internal", "panda_debug_xyzz_internal", "panda_version",
+    "panda_debug_field_op", "panda_debug_curve_op", "panda_debug_fe_internal", "panda_debug_xyzz_internal", "panda_debug_scratch_fill", "panda_version",
     "panda_ntt_table_builds", "panda_msm_set_chunk_first", "panda_set_clock_stamps", "panda_msm_last_clock", "panda_ntt_last_clock", "panda_clock_stamp", "panda_clock_delta",
     "panda_multi_gpu_create", "panda_multi_gpu_destroy", "panda_multi_gpu_device_count", "panda_msm_execute_bn254_multi", "panda_msm_execute_bls12_377_multi",
     "panda_msm_execute_bn254_from_host_multi", "panda_msm_execute_bls12_377_from_host_multi",
@@ -230,6 +230,7 @@ def load() -> C.CDLL:
         "panda_debug_field_op": [u, u, vp, vp, vp, sz, PandaStream], "panda_debug_curve_op": [u, u, vp, vp, vp, sz, PandaStream],
         "panda_debug_fe_internal": [u, u, vp, vp, vp, vp, vp, sz, PandaStream],
         "panda_debug_xyzz_internal": [u, u, vp, vp, vp, sz, PandaStream],
+        "panda_debug_scratch_fill": [u, u, C.POINTER(vp), C.POINTER(sz)],
         "panda_ntt_table_builds": [C.POINTER(C.c_uint64)], "panda_msm_set_chunk_first": [u], "panda_set_clock_stamps": [u], "panda_msm_last_clock": [C.POINTER(C.c_uint64)],
         "panda_ntt_last_clock": [C.POINTER(C.c_uint64)], "panda_clock_stamp": [PandaStream, vp], "panda_clock_delta": [vp, vp, C.POINTER(C.c_uint64)],
         "panda_multi_gpu_create": [C.POINTER(PandaMultiGpu), C.POINTER(C.c_int), u, u], "panda_multi_gpu_destroy": [PandaMultiGpu],

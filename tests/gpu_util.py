@@ -1,5 +1,6 @@
 """Small helpers for the tests: device buffers through the C ABI's own panda_malloc/panda_memcpy, plain and guarded, the device fixture,
-and the checks every feature's test module makes of its exports and of its host-check program."""
+the checks every feature's test module makes of its exports and of its host-check program, and the protocol that runs a call on scratch
+filled through panda_debug_scratch_fill (independent_of_scratch)."""
 import ctypes as C
 import os
 import re
@@ -109,6 +110,66 @@ def free_bytes(lib):
     free, total = C.c_size_t(0), C.c_size_t(0)
     ffi.check(lib.panda_mem_get_info(C.byref(free), C.byref(total)), "mem_info")
     return free.value
+
+
+# ------------------------------------------------------------------------------------------------- what a call finds in its scratch
+# panda_debug_scratch_fill's patterns: every byte 0x00, every byte 0xFF, word i = scratch_hash(i ^ seed).  Both constants are needed: a
+# block that must start as zeros and its neighbour that must start as all-ones each meet what they expect under one of the two.
+SCRATCH_PATTERNS = ((0, 0x00), (0, 0xFF), (1, 0x5CA7C4ED))
+
+
+def scratch_hash(x):
+    """the header's h(x) of panda_debug_scratch_fill, mode 1, on Python integers"""
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = x * 0x7FEB352D & 0xFFFFFFFF
+    x ^= x >> 15
+    x = x * 0x846CA68B & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def scratch_pattern_bytes(mode, value, first_word, words):
+    """what a fill leaves in `words` 32-bit words from word `first_word` of the arena, as uint8"""
+    if mode == 0:
+        return np.full(4 * words, value & 0xFF, np.uint8)
+    return np.array([scratch_hash((first_word + i) ^ value) for i in range(words)], np.uint32).view(np.uint8)
+
+
+def scratch_fill(mode, value):
+    """fill the calling thread's scratch arena and mailbox -> (base, capacity) of the arena, (None, 0) without one"""
+    base, capacity = C.c_void_p(0xDEAD), C.c_size_t(0xDEAD)
+    ffi.check(ffi.load().panda_debug_scratch_fill(mode, value, C.byref(base), C.byref(capacity)), "scratch_fill")
+    return base.value, capacity.value
+
+
+def same_bytes(a, b):
+    """two outputs of a call -- arrays, numbers, bytes or tuples / lists of them -- are identical byte for byte"""
+    if isinstance(a, (tuple, list)):
+        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(same_bytes(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    return type(a) is type(b) and a == b
+
+
+def independent_of_scratch(call, check, exact, arena=True):
+    """The output of call() does not depend on what its scratch held.  call() runs once, which grows the arena to what the call needs, and
+    check(output) compares that output with the reference; then, for every pattern of SCRATCH_PATTERNS, the whole arena and the mailbox are
+    filled, call() runs again on them, and its output is checked again -- and, where `exact` (the call documents a deterministic or
+    canonical output), must be the first run's byte for byte.  The arena's (base, capacity) read with each fill must be what the fill
+    behind the call reads: the call ran on the filled memory, not on a fresh allocation.  arena=False: the call takes no scratch of the
+    arena (the fills then only have to leave its output alone).  Returns the first output."""
+    first = call()
+    check(first)
+    fills = list(SCRATCH_PATTERNS) + [SCRATCH_PATTERNS[0]]
+    where = scratch_fill(*fills[0])
+    for k, pattern in enumerate(SCRATCH_PATTERNS):
+        assert not arena or (where[0] and where[1] > 0), "the call left no scratch arena to fill"
+        out = call()
+        after = scratch_fill(*fills[k + 1])
+        assert after == where, ("the call did not run on the filled arena", pattern, where, after)
+        check(out)
+        assert not exact or same_bytes(out, first), ("the output depends on what the scratch held", pattern)
+    return first
 
 
 def run_host_check(tmp_path, source, *args):

@@ -23,9 +23,18 @@ FAKE = os.path.join(FAKE_DIR, "libfake_rccl.so")
 RCCL_ENTRY_POINTS = ["ncclCommInitAll", "ncclCommDestroy", "ncclGroupStart", "ncclGroupEnd", "ncclAllGather", "ncclSend", "ncclRecv", "ncclGetErrorString"]
 
 
+def _stand_in():
+    """the stand-in's path; built here (the Makefile's one g++ line, host code) when it is missing or older than its source, so that the
+    tests do not depend on a build product having survived under tests/"""
+    src = os.path.join(FAKE_DIR, "fake_rccl.cpp")
+    if not os.path.exists(FAKE) or os.path.getmtime(src) > os.path.getmtime(FAKE):
+        subprocess.run(["make", "-C", FAKE_DIR], check=True, capture_output=True)
+    return FAKE
+
+
 def _child_env(log_path):
     env = dict(os.environ)
-    env["LD_PRELOAD"] = FAKE + (":" + env["LD_PRELOAD"] if env.get("LD_PRELOAD") else "")
+    env["LD_PRELOAD"] = _stand_in() +(":" + env["LD_PRELOAD"] if env.get("LD_PRELOAD") else "")
     env["PANDA_TEST_SHARED_DEVICE_RCCL"] = "1"   # csrc/multi_gpu.hip: several RCCL ranks may name one device
     env["FAKE_RCCL_ALLOW_SHARED_DEVICE"] = "1"   # the stand-in's own duplicate-device check (real RCCL refuses duplicates)
     env["FAKE_RCCL_LOG"] = log_path
@@ -33,9 +42,9 @@ def _child_env(log_path):
 
 
 def test_interposer_covers_every_rccl_symbol_the_library_references():
-    """CPU check: the stand-in is built, exports exactly the RCCL entry points libpanda-cuda.so leaves undefined, and the product
-    library does NOT depend on it (DT_NEEDED names librccl, not the stand-in)."""
-    assert os.path.exists(FAKE), "build it with make -C tests/fake_rccl (or __graft_entry__.build())"
+    """CPU check: the stand-in builds (or is built), exports exactly the RCCL entry points libpanda-cuda.so leaves undefined, and the
+    product library does NOT depend on it (DT_NEEDED names librccl, not the stand-in)."""
+    assert os.path.exists(_stand_in()), "make -C tests/fake_rccl left no libfake_rccl.so"
     lib_path = os.path.join(ROOT, "panda_amd", "csrc", "libpanda-cuda.so")
     undefined = subprocess.run(["nm", "-D", "--undefined-only", lib_path], capture_output=True, text=True, check=True).stdout
     wanted = sorted(line.split()[-1] for line in undefined.splitlines() if line.split()[-1].startswith("nccl"))
