@@ -396,6 +396,51 @@ panda_error panda_poly_divide_linear(unsigned field, const void *d_coeffs, void 
  * point), *launches_divide = those of a division.  None depends on `batch`.  Any pointer may be NULL.  Invalid for the shapes the execute
  * calls refuse (n == 0, batch == 0, batch x n > 2^28). */
 panda_error panda_poly_plan(uint64_t n, unsigned batch, unsigned *tile, unsigned *carry_chunk, unsigned *launches_evaluate, unsigned *launches_divide);
+/* KZG openings of polynomials held as EVALUATIONS (EIP-4844 blobs, PeerDAS cells, Plonk with a Lagrange SRS): the same two steps as the pair
+ * above without a transform.  n = 2^log_n, w = omega a primitive n-th root, s = shift (NULL: 1) the coset shift, x_i = s w^i.  Position j of
+ * a vector holds e_j = f(x_sigma(j)), sigma the identity (PANDA_DOMAIN_NATURAL) or the bit reversal over log_n bits (PANDA_DOMAIN_BITREV);
+ * f is the polynomial of degree < n with those values.
+ *   value:     z^n != s^n: with u = z / s, f(z) = (u^n - 1) / n  sum_i e_i w^i / (u - w^i).  z^n == s^n: z = x_m for one m and f(z) = e_m,
+ *              copied, not computed -- exact at domain points (a challenge may be a root of unity).
+ *   quotient:  q(X) = (f(X) - f(z)) / (X - z), of degree < n - 1, in the form, domain and order of the input: q_i = (e_i - f(z)) / (x_i - z)
+ *              for x_i != z and q_m = -(1 / z) sum_{i != m} q_i x_i at x_m = z.  It is what the MSM takes as scalars: against the Lagrange
+ *              SRS of the same domain and order (panda_ec_ntt, inverse) that MSM is the opening proof.
+ *   field: 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr.  Elements are 32-byte little-endian Montgomery-form residues; vector p starts at byte
+ *     p x n x 32 of d_evals and of d_quot.  batch >= 1, batch x n <= 2^28; log_n == 0 is legal (the value is e_0, the quotient 0).
+ *   omega, shift, points / point: HOST pointers (32 B each, points n_points x 32 B), values below the modulus.  Points of one call may lie on
+ *     and off the domain and may repeat.  values (HOST, batch x n_points x 32 B): f_p(z_k) at element p x n_points + k.  remainders (HOST,
+ *     batch x 32 B, may be NULL): f_p(z).
+ *   Outputs are canonical and the same bytes on every run.  Both calls are synchronous on return; d_quot == d_evals exactly (division in
+ *     place) is legal, otherwise d_evals is only read.  Bytes behind the `batch` vectors of either buffer are never written.
+ *   The domain points and the denominators are computed in the kernels; the host decides z^n == s^n and finds m (log_n steps in the
+ *     2-group).  The denominators are inverted by the product trick with ONE field inversion per call, on the host, for n and all points
+ *     together (the grand product of a point's denominators is u^n - 1, or n / u at a domain point); a call with a shift inverts the
+ *     shift as well.  Evaluation is four kernel launches for all points together and reads d_evals once; division is five.  Every
+ *     further point of an evaluation repeats the inverses: for several points of one polynomial the coefficient-form pair is cheaper.
+ *     No kernel waits for another workgroup.  The scratch (32 bytes per tile, vector and point, and per value) is the calling host
+ *     thread's arena: a repeated call of the same shape allocates nothing, panda_ntt_tear_down releases it.  It never exceeds 64 MiB + 64
+ *     bytes per tile and point: a batch whose vectors x tiles x points exceed 2^21 (only vectors of fewer than 2^11 elements can) runs
+ *     in slices of that many, each with the launches behind the first two of its own.
+ *   panda_error_invalid_value, nothing launched, no output written: field > 2, log_n > 28, batch == 0, batch x n > 2^28, order > 1, n_points
+ *     == 0 or > PANDA_POLY_MAX_POINTS, a NULL buffer, root or point (shift and remainders may be NULL), omega, shift or a point >= the
+ *     modulus, shift == 0, omega not primitive (omega^(n/2) != -1; omega != 1 for log_n == 0), d_quot and d_evals overlapping as address
+ *     ranges without being equal (all checked before any runtime call), and buffers of this library's allocators shorter than stated. */
+#define PANDA_DOMAIN_NATURAL 0u
+#define PANDA_DOMAIN_BITREV 1u
+panda_error panda_poly_evaluate_lagrange(unsigned field, const void *d_evals, unsigned log_n, unsigned batch, const void *omega /* HOST, 32 B */,
+                                         const void *shift /* HOST, 32 B, may be NULL */, unsigned order, const void *points /* HOST, n_points x 32 B */,
+                                         unsigned n_points, void *values /* HOST, batch x n_points x 32 B */, panda_stream stream);
+panda_error panda_poly_divide_linear_lagrange(unsigned field, const void *d_evals, void *d_quot, unsigned log_n, unsigned batch, const void *omega /* HOST, 32 B */,
+                                              const void *shift /* HOST, 32 B, may be NULL */, unsigned order, const void *point /* HOST, 32 B */,
+                                              void *remainders /* HOST, batch x 32 B, may be NULL */, panda_stream stream);
+/* How the two calls run (pure host arithmetic, no device call): *tile = the positions one workgroup covers; the kernels that run one
+ * workgroup per point or vector combine *tile / 2 per-tile partials per step, so they take a second step from tile x tile / 2 positions
+ * on (2^22 for a tile of 2^11).  *launches_evaluate and *launches_divide = the kernel launches of a call (of a call's only slice, see
+ * above), *inversions_per_vector_and_point = an upper bound on the field inversions behind one value or quotient: there is one per
+ * call, on the host, and one more for a shift.  None depends on `batch`.  Any pointer may be NULL.  Invalid for the shapes the execute
+ * calls refuse (log_n > 28, batch == 0, batch x n > 2^28, n_points == 0 or > PANDA_POLY_MAX_POINTS). */
+panda_error panda_poly_lagrange_plan(unsigned log_n, unsigned batch, unsigned n_points, unsigned *tile, unsigned *launches_evaluate, unsigned *launches_divide,
+                                     unsigned *inversions_per_vector_and_point);
 /* Batch inversion and grand products over the scalar fields -- the step between "columns on the device" and "quotient on the coset": the
  * permutation (and lookup) argument's Z(w^0) = 1, Z(w^(i+1)) = Z(w^i) num_i / den_i, and the inverse of a whole vector (logUp denominators,
  * Lagrange and barycentric weights, the 1 / (X - zeta) columns of a batched opening).  field: 0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr;

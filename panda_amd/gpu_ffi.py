@@ -65,6 +65,8 @@ NTT_FORWARD, NTT_INVERSE, NTT_BITREV_OUT, NTT_INVERSE_BITREV_IN, NTT_COSET, NTT_
 NTT_LDE_COSET_MAJOR, NTT_LDE_NATURAL = 0, 1
 NTT_LDE_MAX_LOG_BLOWUP = 4  # PANDA_NTT_LDE_MAX_LOG_BLOWUP
 POLY_MAX_POINTS = 8  # PANDA_POLY_MAX_POINTS
+# `order` of panda_poly_evaluate_lagrange / panda_poly_divide_linear_lagrange (PANDA_DOMAIN_NATURAL, PANDA_DOMAIN_BITREV)
+DOMAIN_NATURAL, DOMAIN_BITREV = 0, 1
 # panda_poly_sum_of_products: the caps of an expression (PANDA_SOP_MAX_*) and its scale modes (PANDA_SOP_SCALE_*)
 SOP_MAX_COLUMNS, SOP_MAX_TERMS, SOP_MAX_FACTORS, SOP_MAX_SCALES = 32, 64, 256, 16
 SOP_SCALE_NONE, SOP_SCALE_PER_VECTOR, SOP_SCALE_CYCLIC = 0, 1, 2
@@ -133,6 +135,7 @@ ADDITIVE_SYMBOLS = [
     "panda_ntt_execute_batch", "panda_ntt_batch_plan",
     "panda_ntt_execute_lde", "panda_ntt_lde_plan",
     "panda_poly_evaluate", "panda_poly_divide_linear", "panda_poly_plan",
+    "panda_poly_evaluate_lagrange", "panda_poly_divide_linear_lagrange", "panda_poly_lagrange_plan",
     "panda_field_batch_inverse", "panda_poly_grand_product", "panda_poly_product_plan",
     "panda_poly_sum_of_products", "panda_poly_sum_of_products_plan",
     "panda_lookup_multiplicities", "panda_lookup_plan", "panda_lookup_home_slot", "panda_poly_running_sum", "panda_poly_running_sum_plan",
@@ -184,6 +187,9 @@ def load() -> C.CDLL:
         "panda_ntt_execute_lde": [u, NttconfigurationV1, vp, u, u, vp, u], "panda_ntt_lde_plan": [u, u, u, u, C.POINTER(u), C.POINTER(u)],
         "panda_poly_evaluate": [u, vp, C.c_uint64, u, vp, u, vp, PandaStream], "panda_poly_divide_linear": [u, vp, vp, C.c_uint64, u, vp, vp, PandaStream],
         "panda_poly_plan": [C.c_uint64, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)],
+        "panda_poly_evaluate_lagrange": [u, vp, u, u, vp, vp, u, vp, u, vp, PandaStream],
+        "panda_poly_divide_linear_lagrange": [u, vp, vp, u, u, vp, vp, u, vp, vp, PandaStream],
+        "panda_poly_lagrange_plan": [u, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)],
         "panda_field_batch_inverse": [u, vp, vp, C.c_uint64, PandaStream], "panda_poly_grand_product": [u, vp, vp, vp, C.c_uint64, u, vp, PandaStream],
         "panda_poly_product_plan": [C.c_uint64, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)],
         "panda_poly_sum_of_products": [u, C.POINTER(SopExpression), vp, C.c_uint64, u, PandaStream],

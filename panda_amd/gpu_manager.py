@@ -650,6 +650,57 @@ def panda_poly_gpu_divide(gm: PandaGpuManager, polys, point, field: int = 0):
     return quotients, remainders
 
 
+def _lagrange_domain(polys_n, omega, shift):
+    """(log_n, omega words, shift pointer or None) of a call on evaluation-form vectors of polys_n elements"""
+    if polys_n & (polys_n - 1):
+        raise PandaGpuError("SchedulingErr")
+    o = np.ascontiguousarray(omega, np.uint32).reshape(8)
+    s = None if shift is None else np.ascontiguousarray(shift, np.uint32).reshape(8)
+    return polys_n.bit_length() - 1, o, s
+
+
+def panda_poly_gpu_evaluate_lagrange(gm: PandaGpuManager, evals, omega, points, field: int = 0, shift=None, order: int = 0) -> np.ndarray:
+    """Additive: the values at up to ffi.POLY_MAX_POINTS points of the polynomials that equal-length vectors of n = 2^k evaluations on
+    the domain shift * omega^i stand for (natural order, or ffi.DOMAIN_BITREV), by ONE library call (panda_poly_evaluate_lagrange)
+    and without a transform; points on the domain return the stored element.  `omega`, `shift` and the rows of `points` are (8,) uint32
+    Montgomery-form elements.  The host arrays are staged into one device buffer and are not changed.  Returns a (batch, n_points, 8)
+    uint32 array; an empty list returns an empty (0, n_points, 8) array without a call."""
+    pts = np.ascontiguousarray(points, np.uint32).reshape(-1, 8)
+    if len(evals) == 0:
+        return np.empty((0, len(pts), 8), np.uint32)
+    lib = ffi.load()
+    d, batch, n = _stage_polys(gm, evals)
+    try:
+        log_n, o, s = _lagrange_domain(n, omega, shift)
+        values = np.empty((batch, len(pts), 8), np.uint32)
+        ffi.check(lib.panda_poly_evaluate_lagrange(field, d, log_n, batch, _ptr(o), None if s is None else _ptr(s), order, _ptr(pts), len(pts), _ptr(values),
+                                                   gm.exec_stream.raw), "SchedulingErr")
+    finally:
+        lib.panda_free(d)
+    return values
+
+
+def panda_poly_gpu_divide_lagrange(gm: PandaGpuManager, evals, omega, point, field: int = 0, shift=None, order: int = 0):
+    """Additive: the quotients (f - f(z)) / (X - z) of evaluation-form vectors, as evaluations on the same domain in the same order, by
+    ONE library call (panda_poly_divide_linear_lagrange) in place on the staged device copy; the host arrays are not changed.  Returns
+    (quotients, remainders): a list of (n, 8) uint32 arrays and a (batch, 8) uint32 array of the values f(z); an empty list returns
+    ([], an empty (0, 8) array) without a call."""
+    if len(evals) == 0:
+        return [], np.empty((0, 8), np.uint32)
+    lib = ffi.load()
+    z = np.ascontiguousarray(point, np.uint32).reshape(8)
+    d, batch, n = _stage_polys(gm, evals)
+    try:
+        log_n, o, s = _lagrange_domain(n, omega, shift)
+        remainders = np.empty((batch, 8), np.uint32)
+        ffi.check(lib.panda_poly_divide_linear_lagrange(field, d, d, log_n, batch, _ptr(o), None if s is None else _ptr(s), order, _ptr(z), _ptr(remainders),
+                                                        gm.exec_stream.raw), "SchedulingErr")
+        quotients = _download_vectors(lib, d, batch, n)
+    finally:
+        lib.panda_free(d)
+    return quotients, remainders
+
+
 def _download_vectors(lib, d, batch, n):
     """the `batch` vectors of n elements at d -> a list of (n, 8) uint32 arrays"""
     size = n * FIELD_ELEMENT_LEN
