@@ -176,6 +176,96 @@ PANDA_HD int xyzz_madd_core(Xyzz<F> &acc, const Fe<F> &bx, const Fe<F> &by)
     return 0;
 }
 
+// ---- the mixed addition on signed limbs (fe29.h, signed contract): the four differences of the formula -- P, R, X3, Q - X3 -- are
+// limb-wise differences with no multiple of p added, and only X3, which is stored and subtracted from again, gets a carry pass.
+//
+// Bounds, in units of p, with H = R / p (169 for BN254).  A signed product is within (T / R, T / R + p), so |product| < |T| / H + 1, and
+// a product of non-negative factors, or a square, is in (0, T / H + 1).  Accumulator on entry (SignedBounds below):
+//   X in (-XN, XS), |Y| < YS, ZZ in (0, ZS), |ZZZ| < ZS;  bx, by in [0, 1) canonical.
+// These hold for a row that has just become the accumulator (X, Y < 1, ZZ = ZZZ = R mod p < 1), for the output of xyzz_dbl_affine
+// once its X is reduced (signed_after_doubling: X < 2; Y, ZZ, ZZZ < 2 tight), and -- the static_asserts -- for the output of this function.
+//   U2  = bx ZZ          in (0, ZS / H + 1)                  unsigned product: both factors are non-negative
+//   P   = U2 - X         |P|   < PS  = max(XS, XN) + ZS / H + 1
+//   S2  = by ZZZ         |S2|  < ZS / H + 1
+//   R   = S2 - Y         |R|   < RS  = YS + ZS / H + 1
+//   PP  = P^2            in (0, PPS = PS^2 / H + 1)           < 2: a square, so non-negative and s-tight: fe_is_zero_2p's input class
+//   PPP = P PP           |PPP| < P3S = PS PPS / H + 1
+//   Q   = X PP           |Q|   < QS  = max(XS, XN) PPS / H + 1
+//   ZZ' = ZZ PP          in (0, ZS PPS / H + 1)               <= ZS      unsigned product
+//   ZZZ'= ZZZ PPP        |ZZZ'| < ZS P3S / H + 1              <= ZS
+//   RR  = R^2            in (0, RS^2 / H + 1)
+//   X3  = RR - 2Q - PPP  in (-(2 QS + P3S), RS^2 / H + 1 + 2 QS + P3S)      within (-XN, XS); limbs in (-3 2^29, 2^29) before the carry
+//                        pass, s-loose after it
+//   v   = Q - X3         |v|   < VS  = QS + max(XS, XN)
+//   Y3  = R v - Y PPP    |Y3|  < (RS VS + YS P3S) / H + 1     <= YS;  the one product pair: RS VS + YS P3S < 0.9 H as well
+// Every limb that enters a product is s-tight, s-loose or the difference of two such: within +-(2^29 + 3).
+template <class F>
+struct SignedBounds {
+    static constexpr double H = (double)F::HEADROOM;
+    static constexpr double XS = 4.4, XN = 3.2, YS = 2.0, ZS = 2.0; // the accumulator on entry
+    static constexpr double XM = XS > XN ? XS : XN;
+    static constexpr double PS = XM + ZS / H + 1, RS = YS + ZS / H + 1;
+    static constexpr double PPS = PS * PS / H + 1, P3S = PS * PPS / H + 1, QS = XM * PPS / H + 1;
+    static constexpr double RRS = RS * RS / H + 1, VS = QS + XM;
+    static_assert(PPS < 2, "PP must stay below 2p for fe_is_zero_2p");
+    static_assert(2 * QS + P3S < XN && RRS + 2 * QS + P3S < XS, "X3 leaves the accumulator's bound");
+    static_assert((RS * VS + YS * P3S) / H + 1 < YS, "Y3 leaves the accumulator's bound");
+    static_assert(ZS * PPS / H + 1 < ZS && ZS * P3S / H + 1 < ZS, "ZZ, ZZZ leave the accumulator's bound");
+    // what a reader of a stored signed accumulator adds to make it unsigned again (fe_from_signed<K>): the stored invariants of
+    // Bounds<F> must hold afterwards -- X < XB p, Y < YB p; ZZZ comes back loose and below 3p, and every use of a stored ZZZ is
+    // as a factor of a product whose other factor is below 3p
+    static constexpr int KX = 4, KY = 1, KZZZ = 1;
+    static_assert(XN < KX - 0.5 && XS + KX <= Bounds<F>::XB, "stored X after the conversion");
+    static_assert((RS * VS + YS * P3S) / H < KY - 0.5 && YS + KY <= Bounds<F>::YB, "stored Y after the conversion");
+    static_assert(ZS * P3S / H < KZZZ - 0.5 && ZS + KZZZ <= 3, "stored ZZZ after the conversion");
+};
+
+// xyzz_dbl_affine's result as the signed addition takes it: X comes out loose and below XB p, beyond SignedBounds::XS -- it is reduced
+// below 2p here, on the rare path, where instructions are free; Y, ZZ, ZZZ are tight and below 2p already.
+template <class F>
+PANDA_HD void signed_after_doubling(Xyzz<F> &acc)
+{
+    fe_reduce_small_2p(acc.X);
+}
+
+// xyzz_madd_core on signed limbs: same formula, same return convention.  bx, by tight and canonical (a negated y is p - y, taken on
+// the packed words: a limb-wise -y would put limbs of 2^30 into R once such a row is the accumulator, and R^2 leaves the column).
+template <class F>
+PANDA_HD int xyzz_madd_core_s(Xyzz<F> &acc, const Fe<F> &bx, const Fe<F> &by)
+{
+    typedef SignedBounds<F> B;
+    (void)sizeof(B);
+    Fe<F> U2, S2, P, R, PP, PPP, Q, X3, Y3, t, rr, v, nppp;
+    fe_mul(U2, bx, acc.ZZ); // non-negative factors: the unsigned product
+    fe_sub_s(P, U2, acc.X);
+    fe_mul_s(S2, by, acc.ZZZ);
+    fe_sub_s(R, S2, acc.Y);
+    fe_sqr_s(PP, P);
+    if (fe_is_zero_2p(PP)) // PP is a square: its representative is non-negative, s-tight and below 2p, so the unsigned test stands
+        return fe_is_zero_mod_p_s(R) ? 1 : 2;
+    fe_mul_s(PPP, P, PP);
+    fe_mul_s(Q, acc.X, PP);
+    fe_mul(acc.ZZ, acc.ZZ, PP); // non-negative factors
+    fe_mul_s(acc.ZZZ, acc.ZZZ, PPP);
+    fe_sqr_s(rr, R);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // Q and PPP are tied to the end of R^2 (no instruction): left free, the compiler forms 2Q + PPP, Q - X3's operands and -PPP ahead
+    // of the squaring and carries them through it, which k_accumulate's 128 registers have no room for
+#pragma unroll
+    for (int i = 0; i < F::N; i++) asm volatile("" : "+v"(Q.l[i]), "+v"(PPP.l[i]) : "v"(rr.l[F::N - 1]));
+#endif
+    fe_add_nr(t, Q, Q);   // limb-wise, two's complement: limbs 0..N-2 in [0, 3 2^29)
+    fe_add_nr(t, t, PPP);
+    fe_sub_s_wide(X3, rr, t); // limbs 0..N-2 in (-3 2^29, 2^29)
+    fe_norm_s(X3, X3);        // stored, and subtracted from again on the next trip: s-loose
+    fe_sub_s(v, Q, X3);
+    fe_neg_s(nppp, PPP);
+    fe_mul_add_s(Y3, R, v, acc.Y, nppp);
+    acc.X = X3;
+    acc.Y = Y3;
+    return 0;
+}
+
 // acc += (bx, by); base_identity <=> the wire x was 0 (affine.cuh:72-75)
 template <class F>
 PANDA_HD void xyzz_madd(Xyzz<F> &acc, const Fe<F> &bx, const Fe<F> &by, bool base_identity)

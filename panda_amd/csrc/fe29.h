@@ -25,6 +25,20 @@
 //   fe_mul(a, b)   needs  limb(a) < 2^30.5, limb(b) < 2^30  and  value(a) * value(b) < 0.9 R p
 //                  gives  tight, value < 2p  (exactly: < a b / R + p)
 //   fe_sub<KB>     needs  value(b) < KB p, limb(b) < 2^31 - 4; gives loose, value < value(a) + KEFF p
+//
+// Signed contract (9-limb prime fields only, SignedLimbsOk; checked by tests/host_check/fe29_signed_host.cpp through
+// tests/test_fe29_signed_host.py).  The same registers read as int32; the value is sum l[i] 2^(29 i) with signed l[i] and may be negative.
+//   limb classes   s-tight : limbs 0..N-2 in [0, 2^29), top limb signed      (outputs of fe_mul_s / fe_sqr_s / fe_mul_add_s; a tight value is s-tight)
+//                  s-loose : limbs 0..N-2 in [-3, 2^29 + 1), top limb signed (outputs of fe_norm_s; a loose value with limbs <= 2^29 + 8 is accepted wherever s-loose is)
+//                  s-diff  : every limb within +-SLIMB_MAX = 2^29 + 16       (fe_sub_s of two of the above, fe_neg_s)
+//   fe_mul_s(a, b), fe_sqr_s(a), fe_mul_add_s(a, b, c, d)
+//                  needs  every limb of every operand, the top one included, within +-SLIMB_MAX (any of the three classes)
+//                  gives  s-tight, T / R <= value < T / R + p for the signed T = a b (a^2, a b + c d): the quotient m is in [0, R)
+//                  column 2 N SLIMB_MAX^2 + N 2^58 + carry < 2^63 (fe_signed_columns_fit): 27 2^58 (1 + 2^-24) < 2^62.76 for N = 9; the
+//                  unsigned column uses 2^64 of room, this one has 2^63, which is why the 14-limb fields keep the unsigned code
+//   fe_sub_s(a, b) needs  a, b s-tight or s-loose; gives s-diff, value(a) - value(b) exactly: no multiple of p is added
+//   fe_norm_s(t)   needs  limbs 0..N-2 in [-3 2^29, 2^30); gives s-loose, same value
+//   fe_from_signed<K>(a)  needs a s-tight or s-loose, value(a) > -(K - 1/2) p; gives loose (unsigned), value(a) + K p
 #pragma once
 #include <stdint.h>
 
@@ -61,6 +75,28 @@
 #define FE29_MAC_CONST(acc, x, c) acc += (u64)(x) * (c)
 #endif
 
+// The signed spellings (the signed contract above): both factors are int32 limbs, the accumulator is the same 64-bit register in two's
+// complement.  The wide shadow is signed as well and must stay within 63 bits and a sign.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(FE29_NO_ASM)
+#define FE29_MAC_S(acc, x, y) asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(x), "v"(y) : "vcc")
+#else
+#define FE29_MAC_S(acc, x, y) acc += (u64)((int64_t)(int32_t)(x) * (int32_t)(y))
+#endif
+#if defined(FE29_CHECK)
+#define FE29_SHADOW_DECL_S __int128 shadow = 0;
+#define FE29_SHADOW_MAC_S(x, y) shadow += (__int128)(int32_t)(x) * (int32_t)(y);
+#define FE29_SHADOW_SHIFT_S()                                                                                                      \
+    assert(shadow >= -((__int128)1 << 63) && shadow < ((__int128)1 << 63) && "fe29 signed column accumulator overflow");          \
+    assert((int64_t)acc == (int64_t)shadow && "fe29 signed column differs from its shadow");                                       \
+    shadow >>= 29;
+#define FE29_CHECK_SLIMB(x) assert((int32_t)(x) >= -(int32_t)SLIMB_MAX && (int32_t)(x) <= (int32_t)SLIMB_MAX && "fe29 signed operand limb range")
+#else
+#define FE29_SHADOW_DECL_S
+#define FE29_SHADOW_MAC_S(x, y)
+#define FE29_SHADOW_SHIFT_S()
+#define FE29_CHECK_SLIMB(x)
+#endif
+
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(FE29_NO_ASM)
 #define FE29_DEVICE_CHAINS 1
 #include <utility>
@@ -74,6 +110,7 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 constexpr u32 LIMB_BITS = 29;
 constexpr u32 LIMB_MASK = (1u << 29) - 1;
+constexpr u32 SLIMB_MAX = (1u << 29) + 16; // magnitude of a signed limb that may enter a product (the signed contract)
 
 template <class F>
 struct Fe {
@@ -137,7 +174,7 @@ PANDA_HD bool fe_all_zero(const Fe<F> &a)
 // Device spelling of the product-scanning columns: the multiply-adds of a column go out as two or three asm blocks
 // (MacChain, fe29_chain.h) instead of one asm statement each, which keeps hipcc from separating them with s_nop:
 // +3.5 % multiplications/s at four waves per SIMD, +15 % at three (tools/ubench_mul.hip).
-template <class F, int K>
+template <class F, int K, bool SGN = false>
 __device__ inline __attribute__((always_inline)) void fe29_reduce_col(uint64_t &acc, uint32_t *m, uint32_t *out)
 {
     constexpr int N = F::N;
@@ -158,7 +195,10 @@ __device__ inline __attribute__((always_inline)) void fe29_reduce_col(uint64_t &
             MacChain<2 * N - 1 - K>::vs(acc, m + (K - N + 1), &F::P[N - 1]);
         out[K - N] = (uint32_t)acc & ((1u << 29) - 1);
     }
-    acc >>= 29;
+    if constexpr (SGN)
+        acc = (uint64_t)((int64_t)acc >> 29); // a signed column (fe_mul_s ...): v_ashrrev_i64
+    else
+        acc >>= 29;
 }
 template <class F, int K>
 __device__ inline __attribute__((always_inline)) void fe29_mul_col(uint64_t &acc, const uint32_t *a, const uint32_t *b, uint32_t *m, uint32_t *out)
@@ -217,6 +257,66 @@ template <class F, int... K>
 __device__ inline __attribute__((always_inline)) void fe29_sqr_cols(uint64_t &acc, const uint32_t *a, const uint32_t *a2, uint32_t *m, uint32_t *out, std::integer_sequence<int, K...>)
 {
     (fe29_sqr_col<F, K>(acc, a, a2, m, out), ...);
+}
+// The signed columns (fe_mul_s, fe_sqr_s, fe_mul_add_s): the operand products are v_mad_i64_i32 chains (MacChain::vvi), the products
+// m_i * p_j -- both factors non-negative -- stay v_mad_u64_u32, and the column shift is arithmetic.
+template <class F, int K>
+__device__ inline __attribute__((always_inline)) void fe29_mul_col_s(uint64_t &acc, const uint32_t *a, const uint32_t *b, uint32_t *m, uint32_t *out)
+{
+    constexpr int N = F::N;
+    if constexpr (K == 0)
+        MacChain<1>::vvi0(acc, a, b);
+    else if constexpr (K < N)
+        MacChain<K + 1>::vvi(acc, a, b + K);
+    else
+        MacChain<2 * N - 1 - K>::vvi(acc, a + (K - N + 1), b + (N - 1));
+    fe29_reduce_col<F, K, true>(acc, m, out);
+}
+template <class F, int K>
+__device__ inline __attribute__((always_inline)) void fe29_sqr_col_s(uint64_t &acc, const uint32_t *a, const uint32_t *a2, uint32_t *m, uint32_t *out)
+{
+    constexpr int N = F::N;
+    constexpr int I0 = K < N ? 0 : K - N + 1;
+    constexpr int CNT = (K + 1) / 2 - I0;
+    MacChain<CNT>::vvi(acc, a2 + I0, a + (K - I0));
+    if constexpr (K == 0)
+        MacChain<1>::vvi0(acc, a, a);
+    else if constexpr ((K & 1) == 0)
+        MacChain<1>::vvi(acc, a + K / 2, a + K / 2);
+    fe29_reduce_col<F, K, true>(acc, m, out);
+}
+template <class F, int K>
+__device__ inline __attribute__((always_inline)) void fe29_mul_add_col_s(uint64_t &acc, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, uint32_t *m,
+                                                                         uint32_t *out)
+{
+    constexpr int N = F::N;
+    if constexpr (K == 0) {
+        MacChain<1>::vvi0(acc, a, b);
+        MacChain<1>::vvi(acc, c, d);
+    } else if constexpr (K < N) {
+        MacChain<K + 1>::vvi(acc, a, b + K);
+        MacChain<K + 1>::vvi(acc, c, d + K);
+    } else {
+        MacChain<2 * N - 1 - K>::vvi(acc, a + (K - N + 1), b + (N - 1));
+        MacChain<2 * N - 1 - K>::vvi(acc, c + (K - N + 1), d + (N - 1));
+    }
+    fe29_reduce_col<F, K, true>(acc, m, out);
+}
+template <class F, int... K>
+__device__ inline __attribute__((always_inline)) void fe29_mul_cols_s(uint64_t &acc, const uint32_t *a, const uint32_t *b, uint32_t *m, uint32_t *out, std::integer_sequence<int, K...>)
+{
+    (fe29_mul_col_s<F, K>(acc, a, b, m, out), ...);
+}
+template <class F, int... K>
+__device__ inline __attribute__((always_inline)) void fe29_sqr_cols_s(uint64_t &acc, const uint32_t *a, const uint32_t *a2, uint32_t *m, uint32_t *out, std::integer_sequence<int, K...>)
+{
+    (fe29_sqr_col_s<F, K>(acc, a, a2, m, out), ...);
+}
+template <class F, int... K>
+__device__ inline __attribute__((always_inline)) void fe29_mul_add_cols_s(uint64_t &acc, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
+                                                                          uint32_t *m, uint32_t *out, std::integer_sequence<int, K...>)
+{
+    (fe29_mul_add_col_s<F, K>(acc, a, b, c, d, m, out), ...);
 }
 #endif
 
@@ -566,6 +666,304 @@ PANDA_HD void fe_neg(Fe<F> &r, const Fe<F> &a)
     }
 }
 
+// ------------------------------------------------------------------ signed limbs (the signed contract at the top of the file)
+//
+// The limbs sit in the same u32 registers and are read as int32.  A difference is then the limb-wise difference and nothing else: no
+// multiple of p, no carry pass.  Only fields whose widest column (fe_mul_add_s: 2 N operand products and N products m p) fits 63 bits
+// and a sign take part.
+template <class F>
+struct SignedLimbsOk {
+    static constexpr bool value = !IsExt2<F>::value && F::N <= 9;
+};
+template <class F>
+PANDA_HD constexpr bool fe_signed_columns_fit()
+{
+    // 2 N products of two operand limbs, N products of a quotient digit and a limb of p (both below 2^29), the carry from the column below
+    return 2ull * F::N * ((u64)SLIMB_MAX * SLIMB_MAX) + (u64)F::N * (1ull << 58) + (1ull << 35) < (1ull << 63);
+}
+
+// r = a * b / R mod p on signed limbs.  Product scanning as fe_mul; the quotient digit is taken from the low 29 bits of the column in
+// two's complement, so column + m p is a multiple of 2^29 whatever its sign, and the shift is arithmetic.
+template <class F>
+PANDA_HD void fe_mul_s(Fe<F> &r, const Fe<F> &a, const Fe<F> &b)
+{
+    constexpr int N = F::N;
+    static_assert(SignedLimbsOk<F>::value && fe_signed_columns_fit<F>(), "signed column accumulator too narrow");
+    u32 m[N];
+    u32 out[N];
+    u64 acc = 0;
+#if defined(FE29_DEVICE_CHAINS)
+    fe29_mul_cols_s<F>(acc, a.l, b.l, m, out, std::make_integer_sequence<int, 2 * N - 1>());
+    out[N - 1] = (u32)acc;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.l[i] = out[i];
+    return;
+#endif
+    FE29_SHADOW_DECL_S
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        FE29_CHECK_SLIMB(a.l[i]);
+        FE29_CHECK_SLIMB(b.l[i]);
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+#pragma unroll
+        for (int i = 0; i <= k; i++) {
+            FE29_MAC_S(acc, a.l[i], b.l[k - i]);
+            FE29_SHADOW_MAC_S(a.l[i], b.l[k - i])
+        }
+#pragma unroll
+        for (int i = 0; i < k; i++) {
+            FE29_MAC_CONST(acc, m[i], F::P[k - i]);
+            FE29_SHADOW_MAC_S(m[i], F::P[k - i])
+        }
+        m[k] = ((u32)acc * F::INV) & LIMB_MASK;
+        FE29_MAC_CONST(acc, m[k], F::P[0]);
+        FE29_SHADOW_MAC_S(m[k], F::P[0])
+        FE29_SHADOW_SHIFT_S()
+        acc = (u64)((int64_t)acc >> LIMB_BITS);
+    }
+#pragma unroll
+    for (int k = N; k < 2 * N - 1; k++) {
+#pragma unroll
+        for (int i = k - N + 1; i < N; i++) {
+            FE29_MAC_S(acc, a.l[i], b.l[k - i]);
+            FE29_SHADOW_MAC_S(a.l[i], b.l[k - i])
+        }
+#pragma unroll
+        for (int i = k - N + 1; i < N; i++) {
+            FE29_MAC_CONST(acc, m[i], F::P[k - i]);
+            FE29_SHADOW_MAC_S(m[i], F::P[k - i])
+        }
+        out[k - N] = (u32)acc & LIMB_MASK;
+        FE29_SHADOW_SHIFT_S()
+        acc = (u64)((int64_t)acc >> LIMB_BITS);
+    }
+    out[N - 1] = (u32)acc;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.l[i] = out[i];
+}
+
+// r = (a*b + c*d) / R mod p on signed limbs, one reduction for both products: the widest signed column (fe_signed_columns_fit)
+template <class F>
+PANDA_HD void fe_mul_add_s(Fe<F> &r, const Fe<F> &a, const Fe<F> &b, const Fe<F> &c, const Fe<F> &d)
+{
+    constexpr int N = F::N;
+    static_assert(SignedLimbsOk<F>::value && fe_signed_columns_fit<F>(), "signed column accumulator too narrow");
+    u32 m[N];
+    u32 out[N];
+    u64 acc = 0;
+#if defined(FE29_DEVICE_CHAINS)
+    fe29_mul_add_cols_s<F>(acc, a.l, b.l, c.l, d.l, m, out, std::make_integer_sequence<int, 2 * N - 1>());
+    out[N - 1] = (u32)acc;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.l[i] = out[i];
+    return;
+#endif
+    FE29_SHADOW_DECL_S
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        FE29_CHECK_SLIMB(a.l[i]);
+        FE29_CHECK_SLIMB(b.l[i]);
+        FE29_CHECK_SLIMB(c.l[i]);
+        FE29_CHECK_SLIMB(d.l[i]);
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+#pragma unroll
+        for (int i = 0; i <= k; i++) {
+            FE29_MAC_S(acc, a.l[i], b.l[k - i]);
+            FE29_SHADOW_MAC_S(a.l[i], b.l[k - i])
+            FE29_MAC_S(acc, c.l[i], d.l[k - i]);
+            FE29_SHADOW_MAC_S(c.l[i], d.l[k - i])
+        }
+#pragma unroll
+        for (int i = 0; i < k; i++) {
+            FE29_MAC_CONST(acc, m[i], F::P[k - i]);
+            FE29_SHADOW_MAC_S(m[i], F::P[k - i])
+        }
+        m[k] = ((u32)acc * F::INV) & LIMB_MASK;
+        FE29_MAC_CONST(acc, m[k], F::P[0]);
+        FE29_SHADOW_MAC_S(m[k], F::P[0])
+        FE29_SHADOW_SHIFT_S()
+        acc = (u64)((int64_t)acc >> LIMB_BITS);
+    }
+#pragma unroll
+    for (int k = N; k < 2 * N - 1; k++) {
+#pragma unroll
+        for (int i = k - N + 1; i < N; i++) {
+            FE29_MAC_S(acc, a.l[i], b.l[k - i]);
+            FE29_SHADOW_MAC_S(a.l[i], b.l[k - i])
+            FE29_MAC_S(acc, c.l[i], d.l[k - i]);
+            FE29_SHADOW_MAC_S(c.l[i], d.l[k - i])
+        }
+#pragma unroll
+        for (int i = k - N + 1; i < N; i++) {
+            FE29_MAC_CONST(acc, m[i], F::P[k - i]);
+            FE29_SHADOW_MAC_S(m[i], F::P[k - i])
+        }
+        out[k - N] = (u32)acc & LIMB_MASK;
+        FE29_SHADOW_SHIFT_S()
+        acc = (u64)((int64_t)acc >> LIMB_BITS);
+    }
+    out[N - 1] = (u32)acc;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.l[i] = out[i];
+}
+
+// r = a^2 / R mod p on signed limbs; cross terms once, against the doubled operand (|2 a_i| <= 2 SLIMB_MAX fits an int32)
+template <class F>
+PANDA_HD void fe_sqr_s(Fe<F> &r, const Fe<F> &a)
+{
+    constexpr int N = F::N;
+    static_assert(SignedLimbsOk<F>::value && fe_signed_columns_fit<F>(), "signed column accumulator too narrow");
+    u32 m[N], out[N], a2[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) a2[i] = a.l[i] << 1;
+    u64 acc = 0;
+#if defined(FE29_DEVICE_CHAINS)
+    fe29_sqr_cols_s<F>(acc, a.l, a2, m, out, std::make_integer_sequence<int, 2 * N - 1>());
+    out[N - 1] = (u32)acc;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.l[i] = out[i];
+    return;
+#endif
+    FE29_SHADOW_DECL_S
+#pragma unroll
+    for (int i = 0; i < N; i++) FE29_CHECK_SLIMB(a.l[i]);
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+#pragma unroll
+        for (int i = 0; 2 * i < k; i++) {
+            FE29_MAC_S(acc, a2[i], a.l[k - i]);
+            FE29_SHADOW_MAC_S(a2[i], a.l[k - i])
+        }
+        if ((k & 1) == 0) {
+            FE29_MAC_S(acc, a.l[k / 2], a.l[k / 2]);
+            FE29_SHADOW_MAC_S(a.l[k / 2], a.l[k / 2])
+        }
+#pragma unroll
+        for (int i = 0; i < k; i++) {
+            FE29_MAC_CONST(acc, m[i], F::P[k - i]);
+            FE29_SHADOW_MAC_S(m[i], F::P[k - i])
+        }
+        m[k] = ((u32)acc * F::INV) & LIMB_MASK;
+        FE29_MAC_CONST(acc, m[k], F::P[0]);
+        FE29_SHADOW_MAC_S(m[k], F::P[0])
+        FE29_SHADOW_SHIFT_S()
+        acc = (u64)((int64_t)acc >> LIMB_BITS);
+    }
+#pragma unroll
+    for (int k = N; k < 2 * N - 1; k++) {
+#pragma unroll
+        for (int i = k - N + 1; 2 * i < k; i++) {
+            FE29_MAC_S(acc, a2[i], a.l[k - i]);
+            FE29_SHADOW_MAC_S(a2[i], a.l[k - i])
+        }
+        if ((k & 1) == 0) {
+            FE29_MAC_S(acc, a.l[k / 2], a.l[k / 2]);
+            FE29_SHADOW_MAC_S(a.l[k / 2], a.l[k / 2])
+        }
+#pragma unroll
+        for (int i = k - N + 1; i < N; i++) {
+            FE29_MAC_CONST(acc, m[i], F::P[k - i]);
+            FE29_SHADOW_MAC_S(m[i], F::P[k - i])
+        }
+        out[k - N] = (u32)acc & LIMB_MASK;
+        FE29_SHADOW_SHIFT_S()
+        acc = (u64)((int64_t)acc >> LIMB_BITS);
+    }
+    out[N - 1] = (u32)acc;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.l[i] = out[i];
+}
+
+// r = a - b, limb by limb: no multiple of p, no carries.  a, b s-tight or s-loose; the result is s-diff.
+template <class F>
+PANDA_HD void fe_sub_s(Fe<F> &r, const Fe<F> &a, const Fe<F> &b)
+{
+    static_assert(SignedLimbsOk<F>::value, "signed limbs: 9-limb prime fields only");
+#pragma unroll
+    for (int i = 0; i < F::N; i++) {
+        r.l[i] = a.l[i] - b.l[i];
+        FE29_CHECK_SLIMB(r.l[i]);
+    }
+}
+
+// the same for a b whose limbs 0..N-2 are sums of up to three s-tight limbs ([0, 3 2^29)): the result, limbs in (-3 2^29, 2^29 + 1), is
+// the input of fe_norm_s and of nothing else
+template <class F>
+PANDA_HD void fe_sub_s_wide(Fe<F> &r, const Fe<F> &a, const Fe<F> &b)
+{
+    static_assert(SignedLimbsOk<F>::value, "signed limbs: 9-limb prime fields only");
+#pragma unroll
+    for (int i = 0; i < F::N; i++) r.l[i] = a.l[i] - b.l[i];
+}
+
+// r = -a, limb by limb (the result is s-diff: it feeds a product)
+template <class F>
+PANDA_HD void fe_neg_s(Fe<F> &r, const Fe<F> &a)
+{
+    static_assert(SignedLimbsOk<F>::value, "signed limbs: 9-limb prime fields only");
+#pragma unroll
+    for (int i = 0; i < F::N; i++) r.l[i] = 0u - a.l[i];
+}
+
+// one round of parallel signed carries: limbs 0..N-2 in [-2^31, 2^31) in, s-loose out as long as every carry is in [-3, 1] (limbs in
+// [-3 * 2^29, 2^30)); value unchanged.  Shift, mask and add per limb, as fe_norm, with an arithmetic shift.
+template <class F>
+PANDA_HD void fe_norm_s(Fe<F> &r, const Fe<F> &t)
+{
+    constexpr int N = F::N;
+    static_assert(SignedLimbsOk<F>::value, "signed limbs: 9-limb prime fields only");
+    u32 c[N];
+#pragma unroll
+    for (int i = 0; i < N - 1; i++) {
+        c[i] = (u32)((int32_t)t.l[i] >> LIMB_BITS);
+#if defined(FE29_CHECK)
+        assert((int32_t)c[i] >= -3 && (int32_t)c[i] <= 1 && "fe_norm_s carry range");
+#endif
+    }
+    u32 o[N];
+    o[0] = t.l[0] & LIMB_MASK;
+#pragma unroll
+    for (int i = 1; i < N - 1; i++) o[i] = (t.l[i] & LIMB_MASK) + c[i - 1];
+    o[N - 1] = t.l[N - 1] + c[N - 2];
+#pragma unroll
+    for (int i = 0; i < N; i++) r.l[i] = o[i];
+}
+
+// residue zero?  a signed, |value(a)| < 16 p.  a * (R mod p) / R is congruent to a and lies in (-0.1 p, 1.1 p) (|a| / 169 on either
+// side of [0, p)), s-tight: the only multiples of p in reach are 0 and p, and an s-tight value has one representation, so the limb
+// comparison of fe_is_zero_2p decides it.  Rare paths only.
+template <class F>
+PANDA_HD bool fe_is_zero_mod_p_s(const Fe<F> &a)
+{
+    static_assert(F::HEADROOM >= 160, "the bound above is BN254-like: R / p >= 160");
+    Fe<F> one, t;
+    fe_one(one);
+    fe_mul_s(t, a, one);
+    return fe_is_zero_2p(t);
+}
+
+// signed -> unsigned: r = a + KEFF[K] p, loose.  a s-tight or s-loose with value(a) > -(K - 1/2) p and top limb above -KP[K][N-1]
+// (K p's own top limb less 4), and value(a) + KEFF[K] p within what the caller's bounds allow.  KP[K]'s lower limbs are raised by
+// 2^31 - 4, so limbs from -3 up come out positive and below 2^32; one carry pass (fe_norm) then gives loose limbs.
+template <class F, int K>
+PANDA_HD void fe_from_signed(Fe<F> &r, const Fe<F> &a)
+{
+    static_assert(SignedLimbsOk<F>::value && K >= 1 && K <= 200, "signed limbs: 9-limb prime fields only");
+    Fe<F> t;
+#pragma unroll
+    for (int i = 0; i < F::N; i++) {
+#if defined(FE29_CHECK)
+        assert((int64_t)(int32_t)a.l[i] + (int64_t)F::KP[K][i] >= 0 && (int64_t)(int32_t)a.l[i] + (int64_t)F::KP[K][i] < (1ll << 32) && "fe_from_signed limb range");
+#endif
+        t.l[i] = a.l[i] + F::KP[K][i];
+    }
+    fe_norm(r, t);
+}
+
 // 32-bit wire limbs -> 29-bit limbs (same integer); tight
 template <class F>
 PANDA_HD void fe_unpack(Fe<F> &r, const u32 *w)
@@ -601,7 +999,9 @@ PANDA_HD void fe_pack(u32 *w, const Fe<F> &a)
 // r = p - w on the L packed 32-bit words of a canonical value (0 < w < p; r may be w): one borrow chain, L instructions on the device
 // (v_sub_co / v_subb_co), and the result is canonical again, so fe_unpack gives tight limbs.  w == 0 would come back as p, which is
 // not canonical: callers keep zero (the y of an identity row) away from it, or do not look at the result.
-template <class F>
+// LOCAL_P (device): the words of p are moved into their registers HERE, under the caller's branch, instead of being held in registers
+// across the caller's loop -- L - 1 moves per call for L - 1 registers that are free outside it.
+template <class F, bool LOCAL_P = false>
 PANDA_HD void fe_words_neg(u32 *r, const u32 *w)
 {
     static_assert(!IsExt2<F>::value, "prime fields only");
@@ -610,7 +1010,14 @@ PANDA_HD void fe_words_neg(u32 *r, const u32 *w)
     // go through registers: an instruction that takes its borrow from VCC cannot take a literal as well.
     unsigned borrow = 0;
 #pragma unroll
-    for (int i = 0; i < F::L; i++) r[i] = __builtin_subc(F::PW[i], w[i], borrow, &borrow);
+    for (int i = 0; i < F::L; i++) {
+        u32 pw = F::PW[i];
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (LOCAL_P)
+            if (i > 0) asm volatile("v_mov_b32 %0, %1" : "=v"(pw) : "n"(F::PW[i])); // volatile: not hoisted out of the loop around the call
+#endif
+        r[i] = __builtin_subc(pw, w[i], borrow, &borrow);
+    }
 #else
     u32 borrow = 0;
 #pragma unroll

@@ -406,7 +406,7 @@ __global__ void __launch_bounds__(256) k_chunk_first(const u32 *__restrict__ off
 // LDS kernel runs over).  Each item can be built out for a measurement (-DPANDA_ACC_ITEMS=<mask>); the 14-limb and Fq2 kernels never
 // take any of them.
 #ifndef PANDA_ACC_ITEMS
-#define PANDA_ACC_ITEMS 0x3fu
+#define PANDA_ACC_ITEMS 0x7fu
 #endif
 constexpr unsigned ACC_ITEM_ROW_TUPLES = 32u; // the gathered row is carried to the next trip as the loads' own four-word vectors
 constexpr unsigned ACC_ITEM_WORDS_NEG = 1u;  // a negative digit's y is negated on the packed words (fe_words_neg), not limb-wise
@@ -414,6 +414,7 @@ constexpr unsigned ACC_ITEM_Y_IDENTITY = 2u; // a row is tested for the identity
 constexpr unsigned ACC_ITEM_QUAD_SHIFT = 4u; // the four sorted words of a quad are shifted down, not selected by index
 constexpr unsigned ACC_ITEM_ID_FLAG = 8u;    // "the accumulator is the identity" is a lane flag, not an OR over ZZ
 constexpr unsigned ACC_ITEM_BOUNDARY = 16u;  // one place where a row becomes the accumulator, no carry pass on its y, running bucket address
+constexpr unsigned ACC_ITEM_SIGNED_DIFF = 64u; // the addition on signed limbs (xyzz_madd_core_s): P, R, X3, Q - X3 without bias or carry pass
 template <class F>
 struct AccSlim {
     static constexpr bool value = !IsExt2<F>::value && F::N <= 9;
@@ -423,6 +424,29 @@ __host__ __device__ constexpr bool acc_item(unsigned item)
 {
     return AccSlim<F>::value && (PANDA_ACC_ITEMS & item) != 0;
 }
+// What k_accumulate's signed addition (ACC_ITEM_SIGNED_DIFF) stores, and how its readers take it.  Such an accumulator has signed limbs:
+// X is s-loose and may be negative, Y and ZZZ have a signed top limb; ZZ never is negative.  It is stored as it stands -- a conversion
+// there would sit on the run-boundary path, which half of the loop's trips take -- with bit 31 of ZZ's top limb set (that limb is below
+// 2^23).  The identity (all zero) never carries the mark.  The readers of `parts` and of the bucket arrays -- k_fixup, k_fixup_long,
+// k_sum_lines -- load through load_xyzz_stored: a marked point gets the multiples of p of SignedBounds<F> added to X, Y and ZZZ
+// (fe_from_signed: an addition and a carry pass per limb) and then satisfies the stored invariants of curve29.h; an unmarked point --
+// written by k_fixup or by a kernel with the unsigned addition -- is taken as it is, so no bound of xyzz_add moves.
+constexpr u32 STORED_SIGNED_MARK = 0x80000000u;
+template <class F>
+__device__ __forceinline__ void load_xyzz_stored(Xyzz<F> &p, const u32 *src)
+{
+    load_xyzz<F>(p, src);
+    if constexpr (acc_item<F>(ACC_ITEM_SIGNED_DIFF)) {
+        if (p.ZZ.l[F::N - 1] & STORED_SIGNED_MARK) {
+            typedef SignedBounds<F> SB;
+            p.ZZ.l[F::N - 1] &= ~STORED_SIGNED_MARK;
+            fe_from_signed<F, SB::KX>(p.X, p.X);
+            fe_from_signed<F, SB::KY>(p.Y, p.Y);
+            fe_from_signed<F, SB::KZZZ>(p.ZZZ, p.ZZZ);
+        }
+    }
+}
+
 // a converted base as it sits in HBM: 2*L words, all zero for the identity
 template <class F>
 struct PackedBase {
@@ -478,7 +502,8 @@ __device__ __forceinline__ void row_words(PackedBase<F> &b, const PackedRow<F> &
 // xyzz_madd_core, three instructions per limb cheaper; callers that store or square y normalise it first
 // SLIM: the spelling of accumulate_chunk's loop (items 1 and 2 below); every other caller -- k_accumulate_shared, the table kernels --
 // keeps the limb-wise negation and the test over all 2 L words
-template <class F, bool RAW = false, bool SLIM = false>
+// LOCAL_P: fe_words_neg's spelling for a loop with no registers to spare (the signed addition)
+template <class F, bool RAW = false, bool SLIM = false, bool LOCAL_P = false>
 __device__ __forceinline__ void unpack_base(Fe<F> &x, Fe<F> &y, bool &inf, const PackedBase<F> &b, u32 entry)
 {
     constexpr int L = F::L;
@@ -499,7 +524,7 @@ __device__ __forceinline__ void unpack_base(Fe<F> &x, Fe<F> &y, bool &inf, const
         u32 yw[L];
 #pragma unroll
         for (int k = 0; k < L; k++) yw[k] = b.w[L + k];
-        if (entry >> 31) fe_words_neg<F>(yw, b.w + L);
+        if (entry >> 31) fe_words_neg<F, LOCAL_P>(yw, b.w + L);
         fe_unpack(y, yw);
     } else {
         fe_unpack(y, b.w + L);
@@ -623,10 +648,19 @@ __device__ __forceinline__ void accumulate_chunk(const u32 *__restrict__ bases, 
     constexpr bool SLIM_BOUNDARY = ID_FLAG && acc_item<F>(ACC_ITEM_BOUNDARY);
     // a y that may be stored as it comes out of unpack_base: tight (never negated limb-wise) or loose (fe_neg), not raw
     constexpr bool Y_STORABLE = acc_item<F>(ACC_ITEM_WORDS_NEG) || !(ACC_RAW_Y && RawOperandOk<F>::value);
+    // the addition on signed limbs; it takes y canonical (the negation on the packed words), never limb-wise negated
+    // (The LDS-staged row variants, experiments at five waves per SIMD, keep the unsigned addition: they have fewer registers still.)
+    constexpr bool SIGNED = acc_item<F>(ACC_ITEM_SIGNED_DIFF) && acc_item<F>(ACC_ITEM_WORDS_NEG) && !LDSROW;
     // ID_FLAG: the accumulator is the identity (and its registers hold the identity's zeros).  It can only become the identity where
     // this loop makes it so -- at the chunk's start, at a boundary, after P + (-P) -- or by doubling a point of order two.
     bool acc_id = true;
     u32 *brun = bw + (u64)b * PW; // SLIM_BOUNDARY: bucket b's accumulator, moved along with b
+    // SIGNED: the accumulator goes out with its signed limbs and the mark its readers convert it by (load_xyzz_stored).  The mark is
+    // put on the accumulator itself: every store is the last use of the value -- a new run or the end of the chunk follows.
+    auto store_acc = [&](u32 *dst) {
+        if constexpr (SIGNED) acc.ZZ.l[F::N - 1] |= (ID_FLAG ? acc_id : xyzz_is_identity(acc)) ? 0u : STORED_SIGNED_MARK;
+        store_xyzz<F>(dst, acc);
+    };
     if constexpr (QUAD_SHIFT) { // the quad's words come out of .x, one per trip: words 0 and 1 are taken, the next shift brings up word 2
         quad.x = quad.y;
         quad.y = quad.z;
@@ -640,7 +674,7 @@ __device__ __forceinline__ void accumulate_chunk(const u32 *__restrict__ bases, 
         const u32 entry = cur_entry;
         if constexpr (LDSROW) read_base_lds<F>(next_base, lds_wave, lane);
         if constexpr (ROW_TUPLES) row_words<F>(next_base, next_row); // the wait for the row is here, at its first use
-        unpack_base<F, ACC_RAW_Y && RawOperandOk<F>::value, true>(cx, cy, cinf, next_base, entry);
+        unpack_base<F, ACC_RAW_Y && RawOperandOk<F>::value, true, SIGNED>(cx, cy, cinf, next_base, entry);
         if constexpr (ROW_TUPLES) {
             // the row is unpacked HERE, before the next gather is issued into the registers it sits in: left free, the compiler moves the
             // unpacking of x down to the addition, keeps x's eight words alive across the gather, and copies them out of its way
@@ -650,7 +684,7 @@ __device__ __forceinline__ void accumulate_chunk(const u32 *__restrict__ bases, 
         const bool boundary = pos >= next;
         if (boundary) { // the run of bucket b ends here; this entry opens the next run, so it simply becomes the accumulator
             if constexpr (SLIM_BOUNDARY) {
-                store_xyzz<F>(run_starts_inside ? brun : pw, acc); // its end (== pos) is inside the chunk by construction
+                store_acc(run_starts_inside ? brun : pw); // its end (== pos) is inside the chunk by construction
                 run_starts_inside = true;
                 do {
                     b++;
@@ -662,7 +696,7 @@ __device__ __forceinline__ void accumulate_chunk(const u32 *__restrict__ bases, 
                 if (cinf) xyzz_set_identity(acc);
                 acc_id = true;
             } else {
-                store_xyzz<F>(run_starts_inside ? bw + (u64)b * PW : pw, acc); // its end (== pos) is inside the chunk by construction
+                store_acc(run_starts_inside ? bw + (u64)b * PW : pw); // its end (== pos) is inside the chunk by construction
                 run_starts_inside = true;
                 do {
                     b++;
@@ -747,7 +781,11 @@ __device__ __forceinline__ void accumulate_chunk(const u32 *__restrict__ bases, 
             acc_id = false;
             continue;
         }
-        const int rare = xyzz_madd_core(acc, cx, cy);
+        int rare;
+        if constexpr (SIGNED)
+            rare = xyzz_madd_core_s(acc, cx, cy);
+        else
+            rare = xyzz_madd_core(acc, cx, cy);
         if (rare) { // same x as the accumulator: reload the base instead of keeping it live through the common path
             if (rare == 1) {
                 PackedBase<F> again;
@@ -756,6 +794,7 @@ __device__ __forceinline__ void accumulate_chunk(const u32 *__restrict__ bases, 
                 fetch_base<F>(again, bases, same);
                 unpack_base<F, false, true>(cx, cy, cinf, again, same);
                 xyzz_dbl_affine(acc, cx, cy);
+                if constexpr (SIGNED) signed_after_doubling(acc); // the doubling is unsigned; its X goes back under the signed bound
                 acc_id = xyzz_is_identity(acc);
             } else {
                 xyzz_set_identity(acc);
@@ -767,7 +806,7 @@ __device__ __forceinline__ void accumulate_chunk(const u32 *__restrict__ bases, 
     const bool starts_inside = run_starts_inside;
     const bool ends_inside = next <= end;
     u32 *dst = (starts_inside && ends_inside) ? (SLIM_BOUNDARY ? brun : bw + (u64)b * PW) : (starts_inside ? pw + PW : pw);
-    store_xyzz<F>(dst, acc);
+    store_acc(dst);
 }
 
 // PERSIST: the grid is a fixed number of workgroups (a few per CU), all resident at once, whose waves draw their chunks -- 64
@@ -1008,7 +1047,7 @@ __global__ void __launch_bounds__(256) k_fixup(const u32 *__restrict__ off, cons
     const u32 t0 = s / K, t1 = (e - 1) / K;
     if (t0 == t1) { // lies inside one chunk: written by k_accumulate
         if (!MERGE) return;
-        load_xyzz<F>(acc, bucket_acc + ((u64)w * NB + b) * PW);
+        load_xyzz_stored<F>(acc, bucket_acc + ((u64)w * NB + b) * PW);
     } else if (t1 - t0 > LONG_SPAN) {
         u32 slot = atomicAdd(&long_count[w], 1u); // a handful per window at most: (t1 - t0) > LONG_SPAN bounds it by chunks / LONG_SPAN
         if (slot < long_cap) {
@@ -1021,14 +1060,14 @@ __global__ void __launch_bounds__(256) k_fixup(const u32 *__restrict__ off, cons
     } else {
         // (loading the piece of chunk t + 1 under the addition of chunk t's changes nothing: these waves are bound by the additions)
         const u32 *pw = parts + (u64)w * chunks * 2 * PW;
-        load_xyzz<F>(acc, pw + ((u64)t0 * 2 + 1) * PW);
+        load_xyzz_stored<F>(acc, pw + ((u64)t0 * 2 + 1) * PW);
         for (u32 t = t0 + 1; t <= t1; t++) {
-            load_xyzz<F>(q, pw + (u64)t * 2 * PW);
+            load_xyzz_stored<F>(q, pw + (u64)t * 2 * PW);
             xyzz_add_k(acc, q);
         }
     }
     if (MERGE) {
-        load_xyzz<F>(q, total + ((u64)w * NB + b) * PW);
+        load_xyzz_stored<F>(q, total + ((u64)w * NB + b) * PW); // a bucket of the first range that k_accumulate wrote is still as it left it
         xyzz_add_k(acc, q);
         store_xyzz<F>(total + ((u64)w * NB + b) * PW, acc);
     } else
@@ -1051,7 +1090,7 @@ __global__ void __launch_bounds__(256) k_fixup_long(const u32 *__restrict__ part
         Xyzz<F> acc, q;
         xyzz_set_identity(acc);
         for (u32 c = t0 + t; c <= t1; c += 256) {
-            load_xyzz<F>(q, pw + ((u64)c * 2 + (c == t0 ? 1 : 0)) * PW);
+            load_xyzz_stored<F>(q, pw + ((u64)c * 2 + (c == t0 ? 1 : 0)) * PW);
             xyzz_add_k(acc, q);
         }
         store_xyzz<F>(lds + t * PW, acc);
@@ -1066,7 +1105,7 @@ __global__ void __launch_bounds__(256) k_fixup_long(const u32 *__restrict__ part
         }
         if (t == 0) {
             if (add) {
-                load_xyzz<F>(q, dst + ((u64)w * NB + b) * PW);
+                load_xyzz_stored<F>(q, dst + ((u64)w * NB + b) * PW);
                 xyzz_add_k(acc, q);
             }
             store_xyzz<F>(dst + ((u64)w * NB + b) * PW, acc);
@@ -1147,7 +1186,7 @@ __global__ void __launch_bounds__(64) k_sum_lines(const u32 *__restrict__ bucket
     xyzz_set_identity(acc);
 #pragma unroll 1
     for (unsigned i = lane; i < count; i += 64) {
-        load_xyzz<F>(q, src + (u64)i * stride * PW);
+        load_xyzz_stored<F>(q, src + (u64)i * stride * PW);
         xyzz_add_k(acc, q);
     }
     wave_reduce<F>(acc, lds, lane);
