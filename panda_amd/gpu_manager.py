@@ -8,7 +8,8 @@ device, fill the by-value configuration struct, call the library and copy the an
 
 Differences, all deliberate:
   * errors raise PandaGpuError instead of returning Err / unwrapping;
-  * the pinned result buffer is freed (the reference leaks it, unit.rs:67-100);
+  * every buffer and event a call takes is released on every way out (`_Buffers`; the reference leaks the pinned result buffer,
+    unit.rs:67-100, and whatever was staged when a later step fails);
   * cached scalars survive reuse, because the library no longer de-Montgomeryizes in place.
 """
 from __future__ import annotations
@@ -140,12 +141,8 @@ class PandaGpuManager:
 
     @staticmethod
     def init_msm_cached_bases(bases) -> int:  # wrapper.rs:154-169
-        b = _as_bytes(bases)
-        d = C.c_void_p()
-        lib = ffi.load()
-        ffi.check(lib.panda_malloc(C.byref(d), b.size), "CreateContextError")
-        ffi.check(lib.panda_memcpy(d, _ptr(b), b.size), "CreateContextError")
-        return d.value
+        with _Buffers() as b:
+            return b.keep(b.upload_sync(bases)).value
 
     init_msm_cached_scalars = init_msm_cached_bases  # wrapper.rs:171-186: same staging
 
@@ -199,10 +196,8 @@ class PandaGpuManager:
         return self.scalars_len[index] if 0 <= index < len(self.scalars_len) else 0
 
     def wait_h2d(self):  # wrapper.rs:260-266
-        ev = PandaEventHandle()
-        ev.record(self.h2d_stream)
-        self.exec_stream.wait(ev)
-        ev.destroy()
+        with _Buffers(self) as b:
+            b.wait_h2d()
 
     def sync(self):  # wrapper.rs:285-291
         self.h2d_stream.sync()
@@ -225,56 +220,142 @@ class PandaGpuManager:
 
 # ---------------------------------------------------------------------------- gpu_manager/common.rs
 
-def memory_alloc_and_copy(gm: PandaGpuManager, h_values, stream: PandaStreamHandle) -> int:  # common.rs:54-65
-    b = _as_bytes(h_values)
-    d = C.c_void_p()
-    lib = ffi.load()
-    ffi.check(lib.panda_malloc_from_pool_async(C.byref(d), b.size, gm.mem_pool, stream.raw), "AsyncPoolMallocErr")
-    ffi.check(lib.panda_memcpy_async(d, _ptr(b), b.size, stream.raw), "AsyncMemcopyErr")
-    return d.value
+def _vp(d) -> C.c_void_p:
+    return d if isinstance(d, C.c_void_p) else C.c_void_p(d)
 
 
-def _pool_alloc(gm: PandaGpuManager, size: int, stream: PandaStreamHandle) -> int:
-    d = C.c_void_p()
-    ffi.check(ffi.load().panda_malloc_from_pool_async(C.byref(d), size, gm.mem_pool, stream.raw), "AsyncPoolMallocErr")
-    return d.value
+class _Buffers:
+    """What one call takes from the library -- device, pool and pinned buffers, events -- released on every way out: in reverse order,
+    each release attempted whatever the others return, an exception already on its way never replaced; a release that fails on an
+    otherwise clean exit raises CreateContextError.  The only place in this file that allocates or frees (deinit, PandaSparseMatrix.free
+    and PandaKzgOpenAll.close release what keep() handed over).  tests/test_gpu_manager_buffers.py runs every wrapper over it."""
+
+    def __init__(self, gm: "PandaGpuManager | None" = None):
+        self.gm, self.lib, self._owned = gm, ffi.load(), []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        codes = [release(handle) for release, handle in reversed(self._owned)]
+        self._owned = []
+        if exc_type is None and any(codes):
+            raise PandaGpuError("CreateContextError")
+
+    def _own(self, release, handle):
+        self._owned.append((release, handle))
+        return handle
+
+    def keep(self, d):
+        """hand `d` over to an owner that outlives the call: the scope no longer releases it"""
+        self._owned = [(release, handle) for release, handle in self._owned if handle is not d]
+        return d
+
+    def device(self, nbytes: int, kind: str = "AsyncPoolMallocErr") -> C.c_void_p:
+        d = C.c_void_p()
+        ffi.check(self.lib.panda_malloc(C.byref(d), nbytes), kind)
+        return self._own(self.lib.panda_free, d)
+
+    def pool(self, nbytes: int, stream: PandaStreamHandle) -> C.c_void_p:
+        d = C.c_void_p()
+        ffi.check(self.lib.panda_malloc_from_pool_async(C.byref(d), nbytes, self.gm.mem_pool, stream.raw), "AsyncPoolMallocErr")
+        return self._own(self.lib.panda_free, d)
+
+    def pinned(self, nbytes: int) -> C.c_void_p:
+        h = C.c_void_p()
+        ffi.check(self.lib.panda_malloc_host(C.byref(h), nbytes), "CreateContextError")
+        return self._own(self.lib.panda_free_host, h)
+
+    def event(self) -> PandaEventHandle:
+        ev = PandaEventHandle()
+        self._own(self.lib.panda_event_destroy, ev.raw)
+        return ev
+
+    def wait_h2d(self):  # wrapper.rs:260-266
+        ev = self.event()
+        ev.record(self.gm.h2d_stream)
+        self.gm.exec_stream.wait(ev)
+
+    def send(self, d, a: np.ndarray, offset: int = 0):
+        """host array -> d + offset, asynchronously on the h2d stream; returns d"""
+        ffi.check(self.lib.panda_memcpy_async(C.c_void_p(d.value + offset), _ptr(a), a.nbytes, self.gm.h2d_stream.raw), "AsyncMemcopyErr")
+        return d
+
+    def fill(self, d, bufs):
+        """equal-length host arrays -> d, member after member, and the exec stream waits for the copies; returns d"""
+        for k, a in enumerate(bufs):
+            self.send(d, a, k * a.nbytes)
+        self.wait_h2d()
+        return d
+
+    def upload(self, arrays):
+        """equal-length arrays of field elements -> (one device buffer holding them member after member, batch, n)"""
+        bufs = [_as_bytes(a) for a in arrays]
+        size = bufs[0].size
+        if size == 0 or size % FIELD_ELEMENT_LEN or any(a.size != size for a in bufs):
+            raise PandaGpuError("SchedulingErr")
+        return self.fill(self.device(len(bufs) * size), bufs), len(bufs), size // FIELD_ELEMENT_LEN
+
+    def upload_sync(self, a) -> C.c_void_p:
+        """one array -> a device buffer of its own, synchronously"""
+        a = _as_bytes(a)
+        d = self.device(a.size, "CreateContextError")
+        ffi.check(self.lib.panda_memcpy(d, _ptr(a), a.size), "CreateContextError")
+        return d
+
+    def upload_pool(self, a, stream: PandaStreamHandle) -> C.c_void_p:  # common.rs:54-65
+        """one array -> a pool allocation, asynchronously on `stream`"""
+        a = _as_bytes(a)
+        d = self.pool(a.size, stream)
+        ffi.check(self.lib.panda_memcpy_async(d, _ptr(a), a.size, stream.raw), "AsyncMemcopyErr")
+        return d
+
+    def read(self, out: np.ndarray, d) -> np.ndarray:
+        """device -> the host array `out`, synchronously; returns out"""
+        ffi.check(self.lib.panda_memcpy(_ptr(out), _vp(d), out.nbytes), "CreateContextError")
+        return out
+
+    def download(self, d, nbytes: int) -> np.ndarray:
+        return self.read(np.empty(nbytes, np.uint8), d)
+
+    def download_vectors(self, d, batch: int, n: int) -> list:
+        """the `batch` vectors of n elements at d -> a list of (n, 8) uint32 arrays"""
+        size = n * FIELD_ELEMENT_LEN
+        return [self.download(d.value + k * size, size).view(np.uint32).reshape(-1, 8) for k in range(batch)]
+
+
+def memory_alloc_and_copy(gm: PandaGpuManager, h_values, stream: PandaStreamHandle) -> int:  # common.rs:54-65; the caller frees
+    with _Buffers(gm) as b:
+        return b.keep(b.upload_pool(h_values, stream)).value
 
 
 # ---------------------------------------------------------------------------- gpu_manager/unit.rs
 
-def _msm_device(gm, d_scalars, d_bases, log_n, curve, free_scalars, free_bases):
-    lib = ffi.load()
+def _msm_device(b: _Buffers, d_scalars, d_bases, log_n, curve):
+    """the run and the copy back that the four MSM calls share; what the caller staged in `b` goes back with the rest at its exit"""
+    gm, lib = b.gm, b.lib
     nres = _RESULT_BYTES[curve]
-    d_result = _pool_alloc(gm, nres, gm.h2d_stream)
-    gm.wait_h2d()
+    d_result = b.pool(nres, gm.h2d_stream)
+    b.wait_h2d()
     cfg = ffi.MSMConfiguration(gm.mem_pool, gm.exec_stream.raw, d_bases, d_scalars, d_result, log_n, gm.msm_result_coordinate_type)
-    fn = _msm_entry(lib, curve)
-    ffi.check(fn(cfg), "SchedulingErr")
-    ev = PandaEventHandle()
+    ffi.check(_msm_entry(lib, curve)(cfg), "SchedulingErr")
+    ev = b.event()
     ev.record(gm.exec_stream)
     ev.sync()
-    ev.destroy()
-    host = C.c_void_p()
-    ffi.check(lib.panda_malloc_host(C.byref(host), nres), "CreateContextError")
-    try:
-        ffi.check(lib.panda_memcpy(host, C.c_void_p(d_result), nres), "CreateContextError")
-        out = np.frombuffer((C.c_uint8 * nres).from_address(host.value), dtype=np.uint8).copy()
-    finally:
-        lib.panda_free_host(host)
-    for ptr, do in ((d_scalars, free_scalars), (d_bases, free_bases), (d_result, True)):
-        if do:
-            ffi.check(lib.panda_free(C.c_void_p(ptr)), "CreateContextError")
-    return out
+    host = b.pinned(nres)
+    ffi.check(lib.panda_memcpy(host, d_result, nres), "CreateContextError")
+    return np.frombuffer((C.c_uint8 * nres).from_address(host.value), dtype=np.uint8).copy()
 
 
 def panda_msm_bn254_gpu(gm: PandaGpuManager, scalars, bases, curve: int = BN254) -> np.ndarray:
     """unit.rs:10-101: stage scalars and bases, run, return the 96-byte X||Y||Z."""
     s = _as_bytes(scalars)
-    d_scalars = memory_alloc_and_copy(gm, s, gm.h2d_stream)
-    gm.wait_h2d()
-    d_bases = memory_alloc_and_copy(gm, bases, gm.h2d_stream)
-    gm.wait_h2d()
-    return _msm_device(gm, d_scalars, d_bases, log_2(s.size // FIELD_ELEMENT_LEN), curve, True, True)
+    with _Buffers(gm) as b:
+        d_scalars = b.upload_pool(s, gm.h2d_stream)
+        b.wait_h2d()
+        d_bases = b.upload_pool(bases, gm.h2d_stream)
+        b.wait_h2d()
+        return _msm_device(b, d_scalars, d_bases, log_2(s.size // FIELD_ELEMENT_LEN), curve)
 
 
 def pipeline_chunks(log_n: int) -> int:
@@ -294,26 +375,18 @@ def panda_msm_bn254_gpu_with_cached_bases(gm: PandaGpuManager, scalars, bases_in
         raise PandaGpuError("BasesIndexErr")
     log_n = log_2(s.size // FIELD_ELEMENT_LEN)
     chunks = pipeline_chunks(log_n)
-    if d_bases in gm._registered and chunks > 1:
-        lib = ffi.load()
-        nres = _RESULT_BYTES[curve]
-        d_scalars = d_result = None
-        try:  # both buffers go back on every way out, including a failed second allocation or wait
-            d_scalars = _pool_alloc(gm, (1 << log_n) * FIELD_ELEMENT_LEN, gm.h2d_stream)
-            d_result = _pool_alloc(gm, nres, gm.h2d_stream)
-            gm.wait_h2d()
+    with _Buffers(gm) as b:
+        if d_bases in gm._registered and chunks > 1:
+            nres = _RESULT_BYTES[curve]
+            d_scalars = b.pool((1 << log_n) * FIELD_ELEMENT_LEN, gm.h2d_stream)
+            d_result = b.pool(nres, gm.h2d_stream)
+            b.wait_h2d()
             cfg = ffi.MSMConfiguration(gm.mem_pool, gm.exec_stream.raw, d_bases, d_scalars, d_result, log_n, gm.msm_result_coordinate_type)
-            ffi.check(lib.panda_msm_execute_from_host(curve, cfg, _ptr(s), chunks, gm.h2d_stream.raw), "SchedulingErr")
-            out = np.zeros(nres, dtype=np.uint8)
-            ffi.check(lib.panda_memcpy(_ptr(out), C.c_void_p(d_result), nres), "CreateContextError")
-        finally:
-            for d in (d_scalars, d_result):
-                if d is not None:
-                    lib.panda_free(C.c_void_p(d))
-        return out
-    d_scalars = memory_alloc_and_copy(gm, s, gm.h2d_stream)
-    gm.wait_h2d()
-    return _msm_device(gm, d_scalars, d_bases, log_n, curve, True, False)
+            ffi.check(b.lib.panda_msm_execute_from_host(curve, cfg, _ptr(s), chunks, gm.h2d_stream.raw), "SchedulingErr")
+            return b.download(d_result, nres)
+        d_scalars = b.upload_pool(s, gm.h2d_stream)
+        b.wait_h2d()
+        return _msm_device(b, d_scalars, d_bases, log_n, curve)
 
 
 def panda_msm_bn254_gpu_with_cached_bases_batched(gm: PandaGpuManager, scalars_batches, bases_index: int, curve: int = BN254) -> list:
@@ -331,45 +404,31 @@ def panda_msm_bn254_gpu_with_cached_bases_batched(gm: PandaGpuManager, scalars_b
     if any(b.size != size for b in batches):
         raise PandaGpuError("SchedulingErr")
     log_n = log_2(size // FIELD_ELEMENT_LEN)
-    lib = ffi.load()
     nres = _RESULT_BYTES[curve]
-    fn = _msm_entry(lib, curve)
-    slots, results = [], []
-    try:
-        for _ in range(min(2, len(batches))):
-            dev, pin, res = C.c_void_p(), C.c_void_p(), C.c_void_p()
-            ffi.check(lib.panda_malloc(C.byref(dev), size), "AsyncPoolMallocErr")
-            slots.append([dev, pin, res, PandaEventHandle()])
-            ffi.check(lib.panda_malloc_host(C.byref(pin), size), "CreateContextError")
-            slots[-1][1] = pin
-            ffi.check(lib.panda_malloc_host(C.byref(res), nres), "CreateContextError")
-            slots[-1][2] = res
+    results = []
+    with _Buffers(gm) as b:
+        lib = b.lib
+        fn = _msm_entry(lib, curve)
+        try:
+            slots = [(b.device(size), b.event(), b.pinned(size), b.pinned(nres)) for _ in range(min(2, len(batches)))]
 
-        def upload(k):
-            dev, pin, _, ev = slots[k & 1]
-            C.memmove(pin, _ptr(batches[k]), size)  # pageable -> pinned, on the host while the GPU works
-            ffi.check(lib.panda_memcpy_async(dev, pin, size, gm.h2d_stream.raw), "AsyncMemcopyErr")
-            ev.record(gm.h2d_stream)
+            def upload(k):
+                dev, ev, pin, _ = slots[k & 1]
+                C.memmove(pin, _ptr(batches[k]), size)  # pageable -> pinned, on the host while the GPU works
+                ffi.check(lib.panda_memcpy_async(dev, pin, size, gm.h2d_stream.raw), "AsyncMemcopyErr")
+                ev.record(gm.h2d_stream)
 
-        upload(0)
-        for k in range(len(batches)):
-            dev, _, res, ev = slots[k & 1]
-            ffi.check(lib.panda_stream_wait_event(gm.exec_stream.raw, ev.raw), "StreamWaitEventErr")
-            if k + 1 < len(batches):
-                upload(k + 1)  # the other slot: its previous execute has returned, so its buffers are free
-            cfg = ffi.MSMConfiguration(gm.mem_pool, gm.exec_stream.raw, d_bases, dev, res, log_n, gm.msm_result_coordinate_type)
-            ffi.check(fn(cfg), "SchedulingErr")  # synchronous: the result is in `res` on return
-            results.append(np.frombuffer((C.c_uint8 * nres).from_address(res.value), dtype=np.uint8).copy())
-    finally:
-        gm.h2d_stream.sync()
-        for dev, pin, res, ev in slots:
-            ev.destroy()
-            if dev:
-                lib.panda_free(dev)
-            if pin:
-                lib.panda_free_host(pin)
-            if res:
-                lib.panda_free_host(res)
+            upload(0)
+            for k in range(len(batches)):
+                dev, ev, _, res = slots[k & 1]
+                gm.exec_stream.wait(ev)
+                if k + 1 < len(batches):
+                    upload(k + 1)  # the other slot: its previous execute has returned, so its buffers are free
+                cfg = ffi.MSMConfiguration(gm.mem_pool, gm.exec_stream.raw, d_bases, dev, res, log_n, gm.msm_result_coordinate_type)
+                ffi.check(fn(cfg), "SchedulingErr")  # synchronous: the result is in `res` on return
+                results.append(np.frombuffer((C.c_uint8 * nres).from_address(res.value), dtype=np.uint8).copy())
+        finally:
+            gm.h2d_stream.sync()  # no copy may still be on its way into a buffer that the exit frees
     return results
 
 
@@ -388,32 +447,25 @@ def panda_msm_gpu_batch_with_cached_bases(gm: PandaGpuManager, scalars_batches, 
     if any(b.size != size for b in batches):
         raise PandaGpuError("SchedulingErr")
     log_n = log_2(size // FIELD_ELEMENT_LEN)
-    lib = ffi.load()
     nres = _RESULT_BYTES[curve]
-    dev = C.c_void_p()
     out = np.zeros(len(batches) * nres, dtype=np.uint8)  # pageable host memory: the library copies the results out itself
-    try:
-        ffi.check(lib.panda_malloc(C.byref(dev), len(batches) * size), "AsyncPoolMallocErr")
-        for k, b in enumerate(batches):
-            ffi.check(lib.panda_memcpy_async(C.c_void_p(dev.value + k * size), _ptr(b), size, gm.h2d_stream.raw), "AsyncMemcopyErr")
-        gm.wait_h2d()
-        cfg = ffi.MSMConfiguration(gm.mem_pool, gm.exec_stream.raw, d_bases, dev.value, _ptr(out), log_n, gm.msm_result_coordinate_type)
-        ffi.check(lib.panda_msm_execute_batch(curve, cfg, len(batches)), "SchedulingErr")
-    finally:
-        if dev:
-            lib.panda_free(dev)
+    with _Buffers(gm) as b:
+        dev = b.fill(b.device(len(batches) * size), batches)
+        cfg = ffi.MSMConfiguration(gm.mem_pool, gm.exec_stream.raw, d_bases, dev, _ptr(out), log_n, gm.msm_result_coordinate_type)
+        ffi.check(b.lib.panda_msm_execute_batch(curve, cfg, len(batches)), "SchedulingErr")
     return [out[k * nres:(k + 1) * nres].copy() for k in range(len(batches))]
 
 
 def panda_msm_bn254_gpu_with_cached_scalars(gm: PandaGpuManager, scalars_index: int, bases, curve: int = BN254) -> np.ndarray:
     """unit.rs:190-275: n comes from the bases length (len / 64, unit.rs:203)."""
-    b = _as_bytes(bases)
-    d_bases = memory_alloc_and_copy(gm, b, gm.h2d_stream)
-    gm.wait_h2d()
-    d_scalars = gm.get_params_scalars_ptr_mut(scalars_index)
-    if d_scalars is None:
-        raise PandaGpuError("BasesIndexErr")
-    return _msm_device(gm, d_scalars, d_bases, log_2(b.size // _POINT_BYTES[curve]), curve, False, True)
+    h = _as_bytes(bases)
+    with _Buffers(gm) as b:
+        d_bases = b.upload_pool(h, gm.h2d_stream)
+        b.wait_h2d()
+        d_scalars = gm.get_params_scalars_ptr_mut(scalars_index)
+        if d_scalars is None:
+            raise PandaGpuError("BasesIndexErr")
+        return _msm_device(b, d_scalars, d_bases, log_2(h.size // _POINT_BYTES[curve]), curve)
 
 
 def panda_msm_bn254_gpu_with_cached_input(gm: PandaGpuManager, scalars_index: int, bases_index: int, curve: int = BN254) -> np.ndarray:
@@ -423,7 +475,8 @@ def panda_msm_bn254_gpu_with_cached_input(gm: PandaGpuManager, scalars_index: in
     if d_scalars is None or d_bases is None:
         raise PandaGpuError("BasesIndexErr")
     log_n = log_2(gm.get_params_scalars_len(scalars_index) // FIELD_ELEMENT_LEN)
-    return _msm_device(gm, d_scalars, d_bases, log_n, curve, False, False)
+    with _Buffers(gm) as b:
+        return _msm_device(b, d_scalars, d_bases, log_n, curve)
 
 
 def panda_msm_bn254_gpu_host(gm, scalars, bases, curve: int = BN254) -> np.ndarray:
@@ -440,22 +493,19 @@ def panda_msm_bn254_gpu_host(gm, scalars, bases, curve: int = BN254) -> np.ndarr
 
 
 def _ntt(gm, scalars: np.ndarray, log_n: int, call, omega=None):
-    lib = ffi.load()
     buf = _as_bytes(scalars)
     assert buf.size == (1 << log_n) * 32  # unit.rs:423
-    d_src = memory_alloc_and_copy(gm, buf, gm.h2d_stream)
-    d_dst = _pool_alloc(gm, buf.size, gm.h2d_stream)
     flag = C.c_uint(0)
-    if omega is None:
-        cfg = ffi.NTTConfiguration(gm.mem_pool, gm.exec_stream.raw, d_src, d_dst, log_n, C.pointer(flag))
-    else:
-        o = _as_bytes(omega)
-        cfg = ffi.NttconfigurationV1(gm.mem_pool, gm.exec_stream.raw, d_src, d_dst, _ptr(o), log_n, C.pointer(flag))
-    ffi.check(call(cfg), "SchedulingErr")
-    src = d_src if flag.value == 0 else d_dst  # unit.rs:521-532
-    ffi.check(lib.panda_memcpy(_ptr(buf), C.c_void_p(src), buf.size), "CreateContextError")
-    ffi.check(lib.panda_free(C.c_void_p(d_src)), "CreateContextError")
-    ffi.check(lib.panda_free(C.c_void_p(d_dst)), "CreateContextError")
+    with _Buffers(gm) as b:
+        d_src = b.upload_pool(buf, gm.h2d_stream)
+        d_dst = b.pool(buf.size, gm.h2d_stream)
+        if omega is None:
+            cfg = ffi.NTTConfiguration(gm.mem_pool, gm.exec_stream.raw, d_src, d_dst, log_n, C.pointer(flag))
+        else:
+            o = _as_bytes(omega)
+            cfg = ffi.NttconfigurationV1(gm.mem_pool, gm.exec_stream.raw, d_src, d_dst, _ptr(o), log_n, C.pointer(flag))
+        ffi.check(call(cfg), "SchedulingErr")
+        b.read(buf, d_src if flag.value == 0 else d_dst)  # unit.rs:521-532
     return flag.value
 
 
@@ -526,26 +576,17 @@ def panda_ntt_gpu_batch(gm: PandaGpuManager, polys, omega, log_n: int, field: in
     size = (1 << log_n) * FIELD_ELEMENT_LEN
     if any(b.size != size for b in bufs):
         raise PandaGpuError("SchedulingErr")
-    lib = ffi.load()
     o = _as_bytes(omega)
     g = _as_bytes(shift) if shift is not None else None
-    d_src, d_dst = C.c_void_p(), C.c_void_p()
     flag = C.c_uint(0)
-    try:
-        ffi.check(lib.panda_malloc(C.byref(d_src), len(bufs) * size), "AsyncPoolMallocErr")
-        ffi.check(lib.panda_malloc(C.byref(d_dst), len(bufs) * size), "AsyncPoolMallocErr")
-        for k, b in enumerate(bufs):
-            ffi.check(lib.panda_memcpy_async(C.c_void_p(d_src.value + k * size), _ptr(b), size, gm.h2d_stream.raw), "AsyncMemcopyErr")
-        gm.wait_h2d()
+    with _Buffers(gm) as b:
+        d_src, d_dst = b.device(len(bufs) * size), b.device(len(bufs) * size)
+        b.fill(d_src, bufs)
         cfg = ffi.NttconfigurationV1(gm.mem_pool, gm.exec_stream.raw, d_src, d_dst, _ptr(o), log_n, C.pointer(flag))
-        ffi.check(lib.panda_ntt_execute_batch(field, kind, cfg, len(bufs), _ptr(g) if g is not None else None), "SchedulingErr")
+        ffi.check(b.lib.panda_ntt_execute_batch(field, kind, cfg, len(bufs), _ptr(g) if g is not None else None), "SchedulingErr")
         res = d_src.value if flag.value == 0 else d_dst.value
-        for k, b in enumerate(bufs):
-            ffi.check(lib.panda_memcpy(_ptr(b), C.c_void_p(res + k * size), size), "CreateContextError")
-    finally:
-        for d in (d_src, d_dst):
-            if d:
-                lib.panda_free(d)
+        for k, buf in enumerate(bufs):
+            b.read(buf, res + k * size)
     return flag.value
 
 
@@ -562,50 +603,15 @@ def panda_ntt_gpu_lde(gm: PandaGpuManager, polys, omega_N, log_n: int, log_blowu
     size = (1 << log_n) * FIELD_ELEMENT_LEN
     if any(b.size != size for b in bufs):
         raise PandaGpuError("SchedulingErr")
-    lib = ffi.load()
     o, g = _as_bytes(omega_N), _as_bytes(shift)
     big = size << log_blowup
-    d_coeffs, d_src, d_dst = C.c_void_p(), C.c_void_p(), C.c_void_p()
     flag = C.c_uint(0)
-    out = []
-    try:
-        ffi.check(lib.panda_malloc(C.byref(d_coeffs), len(bufs) * size), "AsyncPoolMallocErr")
-        ffi.check(lib.panda_malloc(C.byref(d_src), len(bufs) * big), "AsyncPoolMallocErr")
-        ffi.check(lib.panda_malloc(C.byref(d_dst), len(bufs) * big), "AsyncPoolMallocErr")
-        for k, b in enumerate(bufs):
-            ffi.check(lib.panda_memcpy_async(C.c_void_p(d_coeffs.value + k * size), _ptr(b), size, gm.h2d_stream.raw), "AsyncMemcopyErr")
-        gm.wait_h2d()
+    with _Buffers(gm) as b:
+        d_coeffs, d_src, d_dst = b.device(len(bufs) * size), b.device(len(bufs) * big), b.device(len(bufs) * big)
+        b.fill(d_coeffs, bufs)
         cfg = ffi.NttconfigurationV1(gm.mem_pool, gm.exec_stream.raw, d_src, d_dst, _ptr(o), log_n, C.pointer(flag))
-        ffi.check(lib.panda_ntt_execute_lde(field, cfg, d_coeffs, log_blowup, len(bufs), _ptr(g), order), "SchedulingErr")
-        res = d_src.value if flag.value == 0 else d_dst.value
-        for k in range(len(bufs)):
-            ext = np.empty(big, np.uint8)
-            ffi.check(lib.panda_memcpy(_ptr(ext), C.c_void_p(res + k * big), big), "CreateContextError")
-            out.append(ext.view(np.uint32).reshape(-1, 8))
-    finally:
-        for d in (d_coeffs, d_src, d_dst):
-            if d:
-                lib.panda_free(d)
-    return out
-
-
-def _stage_polys(gm: PandaGpuManager, polys):
-    """equal-length coefficient arrays -> (device buffer, batch, n); the caller frees the buffer"""
-    bufs = [_as_bytes(p) for p in polys]
-    size = bufs[0].size
-    if size == 0 or size % FIELD_ELEMENT_LEN or any(b.size != size for b in bufs):
-        raise PandaGpuError("SchedulingErr")
-    lib = ffi.load()
-    d = C.c_void_p()
-    ffi.check(lib.panda_malloc(C.byref(d), len(bufs) * size), "AsyncPoolMallocErr")
-    try:
-        for k, b in enumerate(bufs):
-            ffi.check(lib.panda_memcpy_async(C.c_void_p(d.value + k * size), _ptr(b), size, gm.h2d_stream.raw), "AsyncMemcopyErr")
-        gm.wait_h2d()
-    except Exception:
-        lib.panda_free(d)
-        raise
-    return d, len(bufs), size // FIELD_ELEMENT_LEN
+        ffi.check(b.lib.panda_ntt_execute_lde(field, cfg, d_coeffs, log_blowup, len(bufs), _ptr(g), order), "SchedulingErr")
+        return b.download_vectors(d_src if flag.value == 0 else d_dst, len(bufs), big // FIELD_ELEMENT_LEN)
 
 
 def panda_poly_gpu_evaluate(gm: PandaGpuManager, polys, points, field: int = 0) -> np.ndarray:
@@ -616,13 +622,10 @@ def panda_poly_gpu_evaluate(gm: PandaGpuManager, polys, points, field: int = 0) 
     pts = np.ascontiguousarray(points, np.uint32).reshape(-1, 8)
     if len(polys) == 0:
         return np.empty((0, len(pts), 8), np.uint32)
-    lib = ffi.load()
-    d, batch, n = _stage_polys(gm, polys)
-    try:
+    with _Buffers(gm) as b:
+        d, batch, n = b.upload(polys)
         values = np.empty((batch, len(pts), 8), np.uint32)
-        ffi.check(lib.panda_poly_evaluate(field, d, n, batch, _ptr(pts), len(pts), _ptr(values), gm.exec_stream.raw), "SchedulingErr")
-    finally:
-        lib.panda_free(d)
+        ffi.check(b.lib.panda_poly_evaluate(field, d, n, batch, _ptr(pts), len(pts), _ptr(values), gm.exec_stream.raw), "SchedulingErr")
     return values
 
 
@@ -633,21 +636,12 @@ def panda_poly_gpu_divide(gm: PandaGpuManager, polys, point, field: int = 0):
     array) without a call."""
     if len(polys) == 0:
         return [], np.empty((0, 8), np.uint32)
-    lib = ffi.load()
     z = np.ascontiguousarray(point, np.uint32).reshape(8)
-    d, batch, n = _stage_polys(gm, polys)
-    quotients = []
-    try:
+    with _Buffers(gm) as b:
+        d, batch, n = b.upload(polys)
         remainders = np.empty((batch, 8), np.uint32)
-        ffi.check(lib.panda_poly_divide_linear(field, d, d, n, batch, _ptr(z), _ptr(remainders), gm.exec_stream.raw), "SchedulingErr")
-        size = n * FIELD_ELEMENT_LEN
-        for k in range(batch):
-            q = np.empty(size, np.uint8)
-            ffi.check(lib.panda_memcpy(_ptr(q), C.c_void_p(d.value + k * size), size), "CreateContextError")
-            quotients.append(q.view(np.uint32).reshape(-1, 8))
-    finally:
-        lib.panda_free(d)
-    return quotients, remainders
+        ffi.check(b.lib.panda_poly_divide_linear(field, d, d, n, batch, _ptr(z), _ptr(remainders), gm.exec_stream.raw), "SchedulingErr")
+        return b.download_vectors(d, batch, n), remainders
 
 
 def _lagrange_domain(polys_n, omega, shift):
@@ -668,15 +662,12 @@ def panda_poly_gpu_evaluate_lagrange(gm: PandaGpuManager, evals, omega, points, 
     pts = np.ascontiguousarray(points, np.uint32).reshape(-1, 8)
     if len(evals) == 0:
         return np.empty((0, len(pts), 8), np.uint32)
-    lib = ffi.load()
-    d, batch, n = _stage_polys(gm, evals)
-    try:
+    with _Buffers(gm) as b:
+        d, batch, n = b.upload(evals)
         log_n, o, s = _lagrange_domain(n, omega, shift)
         values = np.empty((batch, len(pts), 8), np.uint32)
-        ffi.check(lib.panda_poly_evaluate_lagrange(field, d, log_n, batch, _ptr(o), None if s is None else _ptr(s), order, _ptr(pts), len(pts), _ptr(values),
-                                                   gm.exec_stream.raw), "SchedulingErr")
-    finally:
-        lib.panda_free(d)
+        ffi.check(b.lib.panda_poly_evaluate_lagrange(field, d, log_n, batch, _ptr(o), None if s is None else _ptr(s), order, _ptr(pts), len(pts), _ptr(values),
+                                                     gm.exec_stream.raw), "SchedulingErr")
     return values
 
 
@@ -687,29 +678,14 @@ def panda_poly_gpu_divide_lagrange(gm: PandaGpuManager, evals, omega, point, fie
     ([], an empty (0, 8) array) without a call."""
     if len(evals) == 0:
         return [], np.empty((0, 8), np.uint32)
-    lib = ffi.load()
     z = np.ascontiguousarray(point, np.uint32).reshape(8)
-    d, batch, n = _stage_polys(gm, evals)
-    try:
+    with _Buffers(gm) as b:
+        d, batch, n = b.upload(evals)
         log_n, o, s = _lagrange_domain(n, omega, shift)
         remainders = np.empty((batch, 8), np.uint32)
-        ffi.check(lib.panda_poly_divide_linear_lagrange(field, d, d, log_n, batch, _ptr(o), None if s is None else _ptr(s), order, _ptr(z), _ptr(remainders),
-                                                        gm.exec_stream.raw), "SchedulingErr")
-        quotients = _download_vectors(lib, d, batch, n)
-    finally:
-        lib.panda_free(d)
-    return quotients, remainders
-
-
-def _download_vectors(lib, d, batch, n):
-    """the `batch` vectors of n elements at d -> a list of (n, 8) uint32 arrays"""
-    size = n * FIELD_ELEMENT_LEN
-    out = []
-    for k in range(batch):
-        v = np.empty(size, np.uint8)
-        ffi.check(lib.panda_memcpy(_ptr(v), C.c_void_p(d.value + k * size), size), "CreateContextError")
-        out.append(v.view(np.uint32).reshape(-1, 8))
-    return out
+        ffi.check(b.lib.panda_poly_divide_linear_lagrange(field, d, d, log_n, batch, _ptr(o), None if s is None else _ptr(s), order, _ptr(z), _ptr(remainders),
+                                                          gm.exec_stream.raw), "SchedulingErr")
+        return b.download_vectors(d, batch, n), remainders
 
 
 def panda_field_gpu_batch_inverse(gm: PandaGpuManager, values, field: int = 0):
@@ -718,13 +694,10 @@ def panda_field_gpu_batch_inverse(gm: PandaGpuManager, values, field: int = 0):
     device copy); the host arrays are not changed.  Returns a list of (n, 8) uint32 arrays; an empty list returns [] without a call."""
     if len(values) == 0:
         return []
-    lib = ffi.load()
-    d, batch, n = _stage_polys(gm, values)
-    try:
-        ffi.check(lib.panda_field_batch_inverse(field, d, d, batch * n, gm.exec_stream.raw), "SchedulingErr")
-        return _download_vectors(lib, d, batch, n)
-    finally:
-        lib.panda_free(d)
+    with _Buffers(gm) as b:
+        d, batch, n = b.upload(values)
+        ffi.check(b.lib.panda_field_batch_inverse(field, d, d, batch * n, gm.exec_stream.raw), "SchedulingErr")
+        return b.download_vectors(d, batch, n)
 
 
 def panda_poly_gpu_grand_product(gm: PandaGpuManager, nums, dens, field: int = 0):
@@ -736,21 +709,16 @@ def panda_poly_gpu_grand_product(gm: PandaGpuManager, nums, dens, field: int = 0
         return [], np.empty((0, 8), np.uint32)
     if dens is not None and len(dens) != len(nums):
         raise PandaGpuError("SchedulingErr")
-    lib = ffi.load()
-    d_num, batch, n = _stage_polys(gm, nums)
-    d_den = None
-    try:
+    with _Buffers(gm) as b:
+        d_num, batch, n = b.upload(nums)
+        d_den = None
         if dens is not None:
-            d_den, batch_den, n_den = _stage_polys(gm, dens)
+            d_den, batch_den, n_den = b.upload(dens)
             if (batch_den, n_den) != (batch, n):
                 raise PandaGpuError("SchedulingErr")
         totals = np.empty((batch, 8), np.uint32)
-        ffi.check(lib.panda_poly_grand_product(field, d_num, d_den, d_num, n, batch, _ptr(totals), gm.exec_stream.raw), "SchedulingErr")
-        return _download_vectors(lib, d_num, batch, n), totals
-    finally:
-        lib.panda_free(d_num)
-        if d_den is not None:
-            lib.panda_free(d_den)
+        ffi.check(b.lib.panda_poly_grand_product(field, d_num, d_den, d_num, n, batch, _ptr(totals), gm.exec_stream.raw), "SchedulingErr")
+        return b.download_vectors(d_num, batch, n), totals
 
 
 def panda_lookup_gpu_multiplicities(gm: PandaGpuManager, table, columns, field: int = 0):
@@ -761,22 +729,15 @@ def panda_lookup_gpu_multiplicities(gm: PandaGpuManager, table, columns, field: 
     (column << 32) | index of the smallest such pair, 2^64 - 1 when there is none.  The host arrays are not changed."""
     if len(columns) == 0 or len(columns) > ffi.LOOKUP_MAX_COLUMNS:
         raise PandaGpuError("SchedulingErr")
-    lib = ffi.load()
-    d_table, _, n_table = _stage_polys(gm, [table])
-    d_cols = d_mult = None
-    try:
-        d_cols, n_columns, n = _stage_polys(gm, columns)
-        d_mult = C.c_void_p()
-        ffi.check(lib.panda_malloc(C.byref(d_mult), n_table * FIELD_ELEMENT_LEN), "AsyncPoolMallocErr")
+    with _Buffers(gm) as b:
+        d_table, _, n_table = b.upload([table])
+        d_cols, n_columns, n = b.upload(columns)
+        d_mult = b.device(n_table * FIELD_ELEMENT_LEN)
         ptrs = (C.c_void_p * n_columns)(*[d_cols.value + k * n * FIELD_ELEMENT_LEN for k in range(n_columns)])
         missing, first = C.c_uint64(0), C.c_uint64(0)
-        ffi.check(lib.panda_lookup_multiplicities(field, d_table, n_table, ptrs, n_columns, n, d_mult, C.byref(missing), C.byref(first), gm.exec_stream.raw),
+        ffi.check(b.lib.panda_lookup_multiplicities(field, d_table, n_table, ptrs, n_columns, n, d_mult, C.byref(missing), C.byref(first), gm.exec_stream.raw),
                   "SchedulingErr")
-        return _download_vectors(lib, d_mult, 1, n_table)[0], missing.value, first.value
-    finally:
-        for d in (d_table, d_cols, d_mult):
-            if d is not None:
-                lib.panda_free(d)
+        return b.download_vectors(d_mult, 1, n_table)[0], missing.value, first.value
 
 
 def panda_poly_gpu_running_sum(gm: PandaGpuManager, vectors, field: int = 0):
@@ -785,14 +746,11 @@ def panda_poly_gpu_running_sum(gm: PandaGpuManager, vectors, field: int = 0):
     uint32 arrays and a (batch, 8) uint32 array of the full sums.  An empty list returns ([], an empty (0, 8) array) without a call."""
     if len(vectors) == 0:
         return [], np.empty((0, 8), np.uint32)
-    lib = ffi.load()
-    d, batch, n = _stage_polys(gm, vectors)
-    try:
+    with _Buffers(gm) as b:
+        d, batch, n = b.upload(vectors)
         totals = np.empty((batch, 8), np.uint32)
-        ffi.check(lib.panda_poly_running_sum(field, d, d, n, batch, _ptr(totals), gm.exec_stream.raw), "SchedulingErr")
-        return _download_vectors(lib, d, batch, n), totals
-    finally:
-        lib.panda_free(d)
+        ffi.check(b.lib.panda_poly_running_sum(field, d, d, n, batch, _ptr(totals), gm.exec_stream.raw), "SchedulingErr")
+        return b.download_vectors(d, batch, n), totals
 
 
 def panda_poly_gpu_sum_of_products(gm: PandaGpuManager, columns, terms, field: int = 0, scales=None, scale_mode: int = 0) -> np.ndarray:
@@ -813,23 +771,15 @@ def panda_poly_gpu_sum_of_products(gm: PandaGpuManager, columns, terms, field: i
     flat = [(c, r) for _, fs in terms for c, r in fs]
     factors = (ffi.SopFactor * max(len(flat), 1))(*[ffi.SopFactor(c, r) for c, r in flat])
     sc = None if scales is None else np.ascontiguousarray(scales, np.uint32).reshape(-1, 8)
-    lib = ffi.load()
-    d, _, _ = _stage_polys(gm, cols)
-    d_out = C.c_void_p()
-    try:
+    with _Buffers(gm) as b:
+        d, _, _ = b.upload(cols)
         size = batch * n * FIELD_ELEMENT_LEN
-        ffi.check(lib.panda_malloc(C.byref(d_out), size), "AsyncPoolMallocErr")
+        d_out = b.device(size)
         ptrs = (C.c_void_p * len(cols))(*[d.value + k * size for k in range(len(cols))])
         expr = ffi.SopExpression(ptrs, _ptr(coeffs), degrees, factors, None if sc is None else _ptr(sc), len(cols), len(terms),
                                  0 if sc is None else len(sc), scale_mode)
-        ffi.check(lib.panda_poly_sum_of_products(field, C.byref(expr), d_out, n, batch, gm.exec_stream.raw), "SchedulingErr")
-        out = np.empty(shape, np.uint32)
-        ffi.check(lib.panda_memcpy(_ptr(out), d_out, size), "CreateContextError")
-        return out
-    finally:
-        lib.panda_free(d)
-        if d_out:
-            lib.panda_free(d_out)
+        ffi.check(b.lib.panda_poly_sum_of_products(field, C.byref(expr), d_out, n, batch, gm.exec_stream.raw), "SchedulingErr")
+        return b.read(np.empty(shape, np.uint32), d_out)
 
 
 def panda_mle_gpu_eq_table(gm: PandaGpuManager, point, field: int = 0) -> np.ndarray:
@@ -840,17 +790,10 @@ def panda_mle_gpu_eq_table(gm: PandaGpuManager, point, field: int = 0) -> np.nda
     if log_n > 28:
         raise PandaGpuError("SchedulingErr")
     host = pt if log_n else np.zeros((1, 8), np.uint32)
-    lib = ffi.load()
-    d = C.c_void_p()
-    size = FIELD_ELEMENT_LEN << log_n
-    ffi.check(lib.panda_malloc(C.byref(d), size), "AsyncPoolMallocErr")
-    try:
-        ffi.check(lib.panda_mle_eq_table(field, _ptr(host), log_n, d, gm.exec_stream.raw), "SchedulingErr")
-        out = np.empty((1 << log_n, 8), np.uint32)
-        ffi.check(lib.panda_memcpy(_ptr(out), d, size), "CreateContextError")
-        return out
-    finally:
-        lib.panda_free(d)
+    with _Buffers(gm) as b:
+        d = b.device(FIELD_ELEMENT_LEN << log_n)
+        ffi.check(b.lib.panda_mle_eq_table(field, _ptr(host), log_n, d, gm.exec_stream.raw), "SchedulingErr")
+        return b.read(np.empty((1 << log_n, 8), np.uint32), d)
 
 
 def panda_sumcheck_gpu_run(gm: PandaGpuManager, columns, terms, n_evals: int, challenges, field: int = 0, order: int = 0, fused: bool = False):
@@ -875,13 +818,12 @@ def panda_sumcheck_gpu_run(gm: PandaGpuManager, columns, terms, n_evals: int, ch
     degrees = (C.c_uint * len(terms))(*[len(fs) for _, fs in terms])
     flat = [c for _, fs in terms for c in fs]
     factors = (ffi.SopFactor * max(len(flat), 1))(*[ffi.SopFactor(c, 0) for c in flat])
-    lib = ffi.load()
     m = len(cols)
     size = n * FIELD_ELEMENT_LEN
-    d, _, _ = _stage_polys(gm, cols)
-    d_other = C.c_void_p()
-    try:
-        ffi.check(lib.panda_malloc(C.byref(d_other), m * (size // 2)), "AsyncPoolMallocErr")
+    with _Buffers(gm) as b:
+        lib = b.lib
+        d, _, _ = b.upload(cols)
+        d_other = b.device(m * (size // 2))
         stream = gm.exec_stream.raw
         evals = np.zeros((k, n_evals, 8), np.uint32)
         # the tables of round j are 2^(k - j) elements each; set 0 is the staged buffer, set 1 holds at most half-size tables
@@ -909,12 +851,8 @@ def panda_sumcheck_gpu_run(gm: PandaGpuManager, columns, terms, n_evals: int, ch
         ffi.check(lib.panda_mle_fold(field, pointers(cur), pointers(1 - cur), m, 1, order, _ptr(ch[k - 1]), stream), "SchedulingErr")
         final = np.empty((m, 8), np.uint32)
         for c in range(m):
-            ffi.check(lib.panda_memcpy(_ptr(final[c]), C.c_void_p(sets[1 - cur][c]), FIELD_ELEMENT_LEN), "CreateContextError")
+            b.read(final[c], sets[1 - cur][c])
         return evals, final
-    finally:
-        lib.panda_free(d)
-        if d_other:
-            lib.panda_free(d_other)
 
 
 class PandaSparseMatrix:
@@ -933,27 +871,16 @@ class PandaSparseMatrix:
             raise PandaGpuError("SchedulingErr")
         self.gm, self.field = gm, field
         self.n_rows, self.n_cols, self.nnz = len(rp) - 1, int(n_cols), len(cl)
-        lib = ffi.load()
-        self._bufs = []
-        try:
-            ptrs = [self._stage(lib, a) if a.size else None for a in (rp, cl, vals)]
-            gm.wait_h2d()
+        with _Buffers(gm) as b:
+            ptrs = [b.send(b.device(a.nbytes), a) if a.size else None for a in (rp, cl, vals)]
+            b.wait_h2d()
             self.matrix = ffi.CsrMatrix(ptrs[0], ptrs[1], ptrs[2], self.n_rows, self.n_cols, self.nnz)
             defect, where = C.c_uint(0), C.c_uint64(0)
-            ffi.check(lib.panda_sparse_check(field, C.byref(self.matrix), C.byref(defect), C.byref(where), gm.exec_stream.raw), "SchedulingErr")
+            ffi.check(b.lib.panda_sparse_check(field, C.byref(self.matrix), C.byref(defect), C.byref(where), gm.exec_stream.raw), "SchedulingErr")
             if defect.value:
                 at = "" if where.value == 0xFFFFFFFFFFFFFFFF else f" at {where.value}"
                 raise PandaGpuError(f"SparseDefect{defect.value}: {self.DEFECTS.get(defect.value, '?')}{at}")
-        except Exception:
-            self.free()
-            raise
-
-    def _stage(self, lib, a: np.ndarray) -> int:
-        d = C.c_void_p()
-        ffi.check(lib.panda_malloc(C.byref(d), a.nbytes), "AsyncPoolMallocErr")
-        self._bufs.append(d)
-        ffi.check(lib.panda_memcpy_async(d, _ptr(a), a.nbytes, self.gm.h2d_stream.raw), "AsyncMemcopyErr")
-        return d.value
+            self._bufs = [b.keep(d) for d in ptrs if d is not None]
 
     def matvec(self, z) -> np.ndarray:
         """M z for z an (n_cols, 8) or (batch, n_cols, 8) uint32 array by ONE library call (panda_sparse_matvec); returns (n_rows, 8) or
@@ -964,20 +891,11 @@ class PandaSparseMatrix:
         batch = 1 if zs.ndim == 2 else zs.shape[0]
         if batch == 0:
             return np.empty((0, self.n_rows, 8), np.uint32)
-        lib = ffi.load()
-        d_z, _, _ = _stage_polys(self.gm, [zs.reshape(-1, 8)])
-        d_out = C.c_void_p()
-        try:
-            size = batch * self.n_rows * FIELD_ELEMENT_LEN
-            ffi.check(lib.panda_malloc(C.byref(d_out), size), "AsyncPoolMallocErr")
-            ffi.check(lib.panda_sparse_matvec(self.field, C.byref(self.matrix), d_z, d_out, batch, self.gm.exec_stream.raw), "SchedulingErr")
-            out = np.empty((self.n_rows, 8) if zs.ndim == 2 else (batch, self.n_rows, 8), np.uint32)
-            ffi.check(lib.panda_memcpy(_ptr(out), d_out, size), "CreateContextError")
-            return out
-        finally:
-            lib.panda_free(d_z)
-            if d_out:
-                lib.panda_free(d_out)
+        with _Buffers(self.gm) as b:
+            d_z, _, _ = b.upload([zs.reshape(-1, 8)])
+            d_out = b.device(batch * self.n_rows * FIELD_ELEMENT_LEN)
+            ffi.check(b.lib.panda_sparse_matvec(self.field, C.byref(self.matrix), d_z, d_out, batch, self.gm.exec_stream.raw), "SchedulingErr")
+            return b.read(np.empty((self.n_rows, 8) if zs.ndim == 2 else (batch, self.n_rows, 8), np.uint32), d_out)
 
     def free(self):
         lib = ffi.load()
@@ -997,24 +915,12 @@ def panda_sparse_gpu_matvec(gm: PandaGpuManager, row_ptr, col, values, z, n_cols
         m.free()
 
 
-def _stage_bytes(lib, a: np.ndarray) -> C.c_void_p:
-    d = C.c_void_p()
-    ffi.check(lib.panda_malloc(C.byref(d), a.nbytes), "CreateContextError")
-    try:
-        ffi.check(lib.panda_memcpy(d, _ptr(a), a.nbytes), "CreateContextError")
-    except PandaGpuError:
-        lib.panda_free(d)
-        raise
-    return d
-
-
 def panda_ec_ntt_gpu(gm: PandaGpuManager, points, omega, curve: int = BN254, inverse: bool = False) -> np.ndarray:
     """Additive: the discrete Fourier transform of n = 2^k affine G1 points (the MSM's base wire form, x || y, identity <=> x == 0) over
     the group, out[k] = sum_j omega^(jk) P_j, natural order; `omega` is the FORWARD root of order n (one Montgomery-form scalar, 32 B)
     for both directions, and inverse=True uses omega^-1 and multiplies by 1 / n -- the inverse transform of a monomial SRS is the
     Lagrange-basis SRS.  One library call (panda_ec_ntt, in place on the device copy); the host array is not changed.  Returns
     (n, point bytes) uint8: canonical affine points, the identity as all-zero bytes, ready for add_cached_bases.  curve is a G1 id."""
-    lib = ffi.load()
     pb = _POINT_BYTES[curve]
     h = _as_bytes(points)
     n = h.size // pb
@@ -1023,38 +929,26 @@ def panda_ec_ntt_gpu(gm: PandaGpuManager, points, omega, curve: int = BN254, inv
     om = _as_bytes(omega)
     if om.size != FIELD_ELEMENT_LEN:
         raise PandaGpuError("InvalidLengthErr")
-    d = _stage_bytes(lib, h)
-    try:
-        ffi.check(lib.panda_ec_ntt(curve, d, d, log_2(n), ffi.EC_NTT_INVERSE if inverse else ffi.EC_NTT_FORWARD, _ptr(om), gm.exec_stream.raw), "SchedulingErr")
-        out = np.empty(h.size, np.uint8)
-        ffi.check(lib.panda_memcpy(_ptr(out), d, h.size), "CreateContextError")
-    finally:
-        lib.panda_free(d)
-    return out.reshape(n, pb)
+    with _Buffers(gm) as b:
+        d = b.upload_sync(h)
+        ffi.check(b.lib.panda_ec_ntt(curve, d, d, log_2(n), ffi.EC_NTT_INVERSE if inverse else ffi.EC_NTT_FORWARD, _ptr(om), gm.exec_stream.raw), "SchedulingErr")
+        return b.download(d, h.size).reshape(n, pb)
 
 
 def panda_points_gpu_to_affine(gm: PandaGpuManager, points, curve: int = BN254, projective: bool = False) -> np.ndarray:
     """Additive: n result triples X || Y || Z (what the MSM calls return: Jacobian, or homogeneous with projective=True; identity <=>
     Z == 0) -> n affine wire points (canonical, the identity as all-zero bytes) by ONE library call (panda_points_to_affine: one field
     inversion per chunk of points).  Returns (n, point bytes) uint8.  curve is a G1 id."""
-    lib = ffi.load()
     rb, pb = _RESULT_BYTES[curve], _POINT_BYTES[curve]
     h = _as_bytes(points)
     n = h.size // rb
     if n == 0 or n * rb != h.size:
         raise PandaGpuError("InvalidLengthErr")
-    d_in = _stage_bytes(lib, h)
-    d_out = C.c_void_p()
-    try:
-        ffi.check(lib.panda_malloc(C.byref(d_out), n * pb), "CreateContextError")
-        ffi.check(lib.panda_points_to_affine(curve, d_in, PROJECTIVE if projective else JACOBIAN, d_out, n, gm.exec_stream.raw), "SchedulingErr")
-        out = np.empty(n * pb, np.uint8)
-        ffi.check(lib.panda_memcpy(_ptr(out), d_out, n * pb), "CreateContextError")
-    finally:
-        lib.panda_free(d_in)
-        if d_out:
-            lib.panda_free(d_out)
-    return out.reshape(n, pb)
+    with _Buffers(gm) as b:
+        d_in = b.upload_sync(h)
+        d_out = b.device(n * pb, "CreateContextError")
+        ffi.check(b.lib.panda_points_to_affine(curve, d_in, PROJECTIVE if projective else JACOBIAN, d_out, n, gm.exec_stream.raw), "SchedulingErr")
+        return b.download(d_out, n * pb).reshape(n, pb)
 
 
 def panda_points_gpu_scalar_mul(gm: PandaGpuManager, points, scalars, curve: int = BN254, mode: int = ffi.POINTS_MUL_EACH, addend=None) -> np.ndarray:
@@ -1062,7 +956,6 @@ def panda_points_gpu_scalar_mul(gm: PandaGpuManager, points, scalars, curve: int
     call (panda_points_scalar_mul).  `scalars` are Montgomery-form Fr elements of 32 B: n of them with mode POINTS_MUL_EACH (k_i =
     scalars[i]), one with POINTS_MUL_ONE (the same k for every point), two with POINTS_MUL_POWERS ((c, s): k_i = c s^i).  The host arrays
     are not changed.  Returns (n, point bytes) uint8: canonical affine points, the identity as all-zero bytes.  curve is a G1 id."""
-    lib = ffi.load()
     pb = _POINT_BYTES[curve]
     h = _as_bytes(points)
     n = h.size // pb
@@ -1074,24 +967,12 @@ def panda_points_gpu_scalar_mul(gm: PandaGpuManager, points, scalars, curve: int
     if add is not None and add.size != h.size:
         raise PandaGpuError("InvalidLengthErr")
     each = mode == ffi.POINTS_MUL_EACH
-    bufs = []
-    try:
-        d = _stage_bytes(lib, h)
-        bufs.append(d)
-        d_sc = d_add = None
-        if each:
-            d_sc = _stage_bytes(lib, sc)
-            bufs.append(d_sc)
-        if add is not None:
-            d_add = _stage_bytes(lib, add)
-            bufs.append(d_add)
-        ffi.check(lib.panda_points_scalar_mul(curve, mode, d, d_sc, None if each else _ptr(sc), d_add, d, n, gm.exec_stream.raw), "SchedulingErr")
-        out = np.empty(h.size, np.uint8)
-        ffi.check(lib.panda_memcpy(_ptr(out), d, h.size), "CreateContextError")
-    finally:
-        for b in bufs:
-            lib.panda_free(b)
-    return out.reshape(n, pb)
+    with _Buffers(gm) as b:
+        d = b.upload_sync(h)
+        d_sc = b.upload_sync(sc) if each else None
+        d_add = b.upload_sync(add) if add is not None else None
+        ffi.check(b.lib.panda_points_scalar_mul(curve, mode, d, d_sc, None if each else _ptr(sc), d_add, d, n, gm.exec_stream.raw), "SchedulingErr")
+        return b.download(d, h.size).reshape(n, pb)
 
 
 class PandaKzgOpenAll:
@@ -1101,7 +982,6 @@ class PandaKzgOpenAll:
     2n points and the workspace resident; open(coeffs) is one panda_kzg_open_all call; close() frees the device memory."""
 
     def __init__(self, gm: PandaGpuManager, srs, omega2, curve: int = BN254):
-        lib = ffi.load()
         self.gm, self.curve, self.pb = gm, curve, _POINT_BYTES[curve]
         h = _as_bytes(srs)
         n = h.size // self.pb
@@ -1110,38 +990,24 @@ class PandaKzgOpenAll:
             raise PandaGpuError("InvalidLengthErr")
         self.n, self.log_n = n, log_2(n)
         work = C.c_size_t(0)
-        ffi.check(lib.panda_kzg_open_all_plan(curve, self.log_n, C.byref(work), None), "InvalidLengthErr")
+        ffi.check(ffi.load().panda_kzg_open_all_plan(curve, self.log_n, C.byref(work), None), "InvalidLengthErr")
         self.work_bytes = work.value
-        self.d_table, self.d_work, self.d_proofs = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        d_srs = None
-        try:
-            ffi.check(lib.panda_malloc(C.byref(self.d_table), 2 * n * self.pb), "CreateContextError")
-            ffi.check(lib.panda_malloc(C.byref(self.d_work), self.work_bytes), "CreateContextError")
-            ffi.check(lib.panda_malloc(C.byref(self.d_proofs), n * self.pb), "CreateContextError")
-            d_srs = _stage_bytes(lib, h)
-            ffi.check(lib.panda_kzg_open_all_setup(curve, d_srs, self.log_n, _ptr(self.omega2), self.d_table, gm.exec_stream.raw), "SchedulingErr")
-        except PandaGpuError:
-            self.close()
-            raise
-        finally:
-            if d_srs:
-                lib.panda_free(d_srs)
+        with _Buffers(gm) as b:
+            resident = [b.device(nbytes, "CreateContextError") for nbytes in (2 * n * self.pb, self.work_bytes, n * self.pb)]
+            d_srs = b.upload_sync(h)
+            ffi.check(b.lib.panda_kzg_open_all_setup(curve, d_srs, self.log_n, _ptr(self.omega2), resident[0], gm.exec_stream.raw), "SchedulingErr")
+            self.d_table, self.d_work, self.d_proofs = [b.keep(d) for d in resident]
 
     def open(self, coeffs) -> np.ndarray:
         """n Montgomery-form coefficients (32 B each) -> (n, point bytes) uint8: proof j opens the polynomial at omega^j"""
-        lib = ffi.load()
         c = _as_bytes(coeffs)
         if c.size != self.n * FIELD_ELEMENT_LEN or not self.d_table:
             raise PandaGpuError("InvalidLengthErr")
-        d_c = _stage_bytes(lib, c)
-        try:
-            ffi.check(lib.panda_kzg_open_all(self.curve, d_c, self.d_table, self.log_n, _ptr(self.omega2), self.d_work, self.work_bytes, self.d_proofs,
-                                             self.gm.exec_stream.raw), "SchedulingErr")
-            out = np.empty(self.n * self.pb, np.uint8)
-            ffi.check(lib.panda_memcpy(_ptr(out), self.d_proofs, out.size), "CreateContextError")
-        finally:
-            lib.panda_free(d_c)
-        return out.reshape(self.n, self.pb)
+        with _Buffers(self.gm) as b:
+            d_c = b.upload_sync(c)
+            ffi.check(b.lib.panda_kzg_open_all(self.curve, d_c, self.d_table, self.log_n, _ptr(self.omega2), self.d_work, self.work_bytes, self.d_proofs,
+                                               self.gm.exec_stream.raw), "SchedulingErr")
+            return b.download(self.d_proofs, self.n * self.pb).reshape(self.n, self.pb)
 
     def close(self):
         lib = ffi.load()
