@@ -797,6 +797,67 @@ panda_error panda_kzg_open_all_setup(unsigned curve, const void *d_srs /* n poin
 panda_error panda_kzg_open_all(unsigned curve, const void *d_coeffs /* n scalars */, const void *d_table, unsigned log_n, const void *omega2,
                                void *d_work, size_t work_bytes, void *d_proofs /* n points */, panda_stream stream);
 panda_error panda_kzg_open_all_plan(unsigned curve, unsigned log_n, size_t *work_bytes, unsigned *launches);
+/* Poseidon over the scalar fields: the permutation, a sponge hash and a Merkle tree over device-resident elements, so that a transcript,
+ * a witness generator's tree of 2^20 .. 2^24 leaves or the commitment to the rows of a low-degree extension needs no download.  field: 0
+ * BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr; elements are the 32-byte canonical Montgomery wire form of every other call, 16-byte aligned;
+ * a non-canonical DEVICE input is outside the contract (the values are then unspecified, the accesses are not).  The reference has none
+ * of these calls.
+ *
+ * The permutation on a state of t = width elements.  Each of the R_F + R_P rounds adds the round's t constants, applies x -> x^alpha to
+ * every element (a full round: the first and the last R_F / 2) or to state[0] alone (a partial round), and multiplies by the matrix:
+ * new[i] = sum_j mds[i][j] old[j].  This is the plain definition and the one circomlib's poseidon computes.  Results are canonical, byte
+ * for byte the same on every run.  The library does not check that the matrix is MDS: that is the caller's parameter set.
+ *
+ * panda_poseidon_create validates the parameters, derives the device table -- the constants as (w, floor(w R / p)) pairs with the wire
+ * form's factors folded in -- and allocates it with panda_malloc; the host arrays may be freed when it returns.  panda_poseidon_destroy
+ * gives the table back.  A handle belongs to the device that was current at its creation.
+ *
+ * panda_poseidon_permute: n states of t contiguous elements, 1 <= n <= 2^28.  d_out == d_in exactly is in place, any other overlap is
+ * refused.
+ *
+ * panda_poseidon_hash: n messages of len >= 1 elements, one thread each, n x len <= 2^28.  Element j of message i is at d_in + 32 (i
+ * msg_stride + j elem_stride), strides in elements, each <= 2^28: (len, 1) is contiguous messages, (1, n) is row i across len column
+ * vectors of n elements -- the layout panda_ntt_execute_batch and panda_ntt_execute_lde leave, whose loads coalesce.  The state starts as
+ * (tag, 0, .., 0); each chunk of t - 1 elements is added into state[1 ..], the last one zero-padded (encode the length in `tag` if
+ * needed), and the state is permuted after every chunk; d_out[i] is state[0] after the last.  With len <= t - 1 and tag = 0 this is
+ * circomlib's hash.  d_out (n elements) must not overlap the input extent, (n - 1) msg_stride + (len - 1) elem_stride + 1 elements.
+ *
+ * panda_poseidon_merkle_tree: arity a = t - 1 >= 2 (width 2 is refused), n = a^height leaves, height >= 1, n <= 2^28.  d_nodes takes the
+ * (n - 1) / (a - 1) inner nodes level by level from the bottom: level 1 is n / a nodes at offset 0, the root is last;
+ * node = permute: (tag, child_0 .. child_(a-1)), element 0 -- every level is panda_poseidon_hash over the level below with len = a.
+ * `root` (HOST, 32 B, may be NULL) receives the last node.  d_nodes must not overlap d_leaves.  One launch per level while a level has
+ * more than *per_workgroup nodes, then ONE single-workgroup launch for the *top_levels levels above, with a workgroup barrier between two
+ * levels: a tree of 24 levels is 16 launches, not 24.  No kernel waits for another workgroup; no atomics, no flags.
+ *
+ * panda_poseidon_plan (pure host arithmetic): *per_workgroup = the permutations one workgroup covers (it depends on nothing), *nodes =
+ * the node count, level_offset[l - 1] = the element offset of level l = 1 .. height in d_nodes (height entries; an authentication path
+ * reads node (index / a^l) of level l), *top_levels and *launches as above.  Any pointer may be NULL.  Invalid for width < 3, width >
+ * PANDA_POSEIDON_MAX_WIDTH, height == 0 and more than 2^28 leaves.
+ *
+ * All calls but the plan are synchronous on return.  panda_error_invalid_value, nothing launched, nothing written: field > 2, the
+ * parameter ranges in the struct below, a round constant, matrix entry or tag >= the modulus, an alpha that divides p - 1, the shapes
+ * above, a NULL pointer (but `root`), a NULL or destroyed handle, the overlaps above, and buffers of this library's allocators shorter
+ * than stated -- all checked before any runtime call.  No kernel reads or writes outside the stated extents. */
+#define PANDA_POSEIDON_MAX_WIDTH 5
+typedef struct panda_poseidon_params
+{
+    unsigned width;              /* t = rate + 1, 2 .. PANDA_POSEIDON_MAX_WIDTH; state[0] is the capacity element */
+    unsigned alpha;              /* S-box x^alpha: 5, 7, 11 or 17, and alpha must not divide p - 1 */
+    unsigned full_rounds;        /* R_F, even, 2 .. 16: R_F / 2 before and R_F / 2 after the partial rounds */
+    unsigned partial_rounds;     /* R_P, 0 .. 128: S-box on state[0] only */
+    const void *round_constants; /* HOST, (R_F + R_P) x t x 32 B, round-major, wire form, each < modulus */
+    const void *mds;             /* HOST, t x t x 32 B, row-major, wire form: new[i] = sum_j mds[i][j] old[j] */
+} panda_poseidon_params;
+typedef struct panda_poseidon { void *handle; } panda_poseidon; /* as panda_multi_gpu */
+panda_error panda_poseidon_create(unsigned field, const panda_poseidon_params *params, panda_poseidon *out);
+panda_error panda_poseidon_destroy(panda_poseidon p);
+panda_error panda_poseidon_permute(panda_poseidon p, const void *d_in, void *d_out, uint64_t n, panda_stream stream);
+panda_error panda_poseidon_hash(panda_poseidon p, const void *d_in, uint64_t len, uint64_t msg_stride, uint64_t elem_stride,
+                                const void *tag /* HOST, 32 B */, void *d_out, uint64_t n, panda_stream stream);
+panda_error panda_poseidon_merkle_tree(panda_poseidon p, const void *d_leaves, unsigned height, const void *tag /* HOST, 32 B */,
+                                       void *d_nodes, void *root /* HOST, 32 B, may be NULL */, panda_stream stream);
+panda_error panda_poseidon_plan(unsigned width, unsigned height, unsigned *per_workgroup, uint64_t *nodes,
+                                uint64_t *level_offset /* height entries, may be NULL */, unsigned *top_levels, unsigned *launches);
 /* Clock stamps (measurement only; off by default).  With panda_set_clock_stamps(1) an MSM brackets the k_accumulate launch of its last
  * range, and a whole NTT its passes, with a marker kernel in which one wave per CU stores s_memtime (shader cycles) and s_memrealtime
  * (100 MHz); stamps are only compared within one CU (the cycle counter is not chip-wide).  panda_*_last_clock fills PANDA_CLOCK_WORDS u64:

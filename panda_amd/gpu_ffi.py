@@ -80,6 +80,7 @@ EC_NTT_MAX_LOG_N = 26  # PANDA_EC_NTT_MAX_LOG_N
 # `mode` of panda_points_scalar_mul (PANDA_POINTS_MUL_*) and the largest log2 of a panda_kzg_open_all domain
 POINTS_MUL_EACH, POINTS_MUL_ONE, POINTS_MUL_POWERS = 0, 1, 2
 KZG_OPEN_ALL_MAX_LOG_N = 25  # PANDA_KZG_OPEN_ALL_MAX_LOG_N
+POSEIDON_MAX_WIDTH = 5  # PANDA_POSEIDON_MAX_WIDTH
 CLOCK_WORDS, CLOCK_STAMP_BYTES = 12, 32768  # PANDA_CLOCK_WORDS, PANDA_CLOCK_STAMP_BYTES
 
 
@@ -100,6 +101,15 @@ class SopExpression(C.Structure):  # additive: include/panda_interface.h panda_s
 class CsrMatrix(C.Structure):  # additive: include/panda_interface.h panda_csr_matrix; every pointer is a DEVICE pointer
     _fields_ = [("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_values", C.c_void_p), ("n_rows", C.c_uint64), ("n_cols", C.c_uint64),
                 ("nnz", C.c_uint64)]
+
+
+class PoseidonParams(C.Structure):  # additive: include/panda_interface.h panda_poseidon_params; both pointers are HOST pointers
+    _fields_ = [("width", C.c_uint), ("alpha", C.c_uint), ("full_rounds", C.c_uint), ("partial_rounds", C.c_uint), ("round_constants", C.c_void_p),
+                ("mds", C.c_void_p)]
+
+
+class PandaPoseidon(C.Structure):  # additive: include/panda_interface.h panda_poseidon (a parameter set and its device table)
+    _fields_ = [("handle", C.c_void_p)]
 
 
 # every symbol include/panda_interface.h declares; tests assert the library exports each one
@@ -143,6 +153,7 @@ ADDITIVE_SYMBOLS = [
     "panda_sparse_matvec", "panda_sparse_check", "panda_sparse_plan",
     "panda_ec_ntt", "panda_ec_ntt_plan", "panda_points_to_affine", "panda_points_to_affine_plan",
     "panda_points_scalar_mul", "panda_points_scalar_mul_plan", "panda_kzg_open_all_setup", "panda_kzg_open_all", "panda_kzg_open_all_plan",
+    "panda_poseidon_create", "panda_poseidon_destroy", "panda_poseidon_permute", "panda_poseidon_hash", "panda_poseidon_merkle_tree", "panda_poseidon_plan",
 ]
 ALL_SYMBOLS = REFERENCE_SYMBOLS + RUST_ONLY_SYMBOLS + ADDITIVE_SYMBOLS
 
@@ -206,6 +217,11 @@ def load() -> C.CDLL:
         "panda_sparse_matvec": [u, C.POINTER(CsrMatrix), vp, vp, u, PandaStream],
         "panda_sparse_check": [u, C.POINTER(CsrMatrix), C.POINTER(u), C.POINTER(C.c_uint64), PandaStream],
         "panda_sparse_plan": [C.c_uint64, C.c_uint64, C.c_uint64, u, C.POINTER(u), C.POINTER(u), C.POINTER(sz), C.POINTER(u)],
+        "panda_poseidon_create": [u, C.POINTER(PoseidonParams), C.POINTER(PandaPoseidon)], "panda_poseidon_destroy": [PandaPoseidon],
+        "panda_poseidon_permute": [PandaPoseidon, vp, vp, C.c_uint64, PandaStream],
+        "panda_poseidon_hash": [PandaPoseidon, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, PandaStream],
+        "panda_poseidon_merkle_tree": [PandaPoseidon, vp, u, vp, vp, vp, PandaStream],
+        "panda_poseidon_plan": [u, u, C.POINTER(u), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(u), C.POINTER(u)],
         "panda_ec_ntt": [u, vp, vp, u, u, vp, PandaStream], "panda_ec_ntt_plan": [u, u, u, C.POINTER(u), C.POINTER(sz), C.POINTER(u)],
         "panda_points_to_affine": [u, vp, C.c_int, vp, C.c_uint64, PandaStream], "panda_points_to_affine_plan": [C.c_uint64, C.POINTER(u), C.POINTER(u)],
         "panda_points_scalar_mul": [u, u, vp, vp, vp, vp, vp, C.c_uint64, PandaStream], "panda_points_scalar_mul_plan": [u, u, C.c_uint64, C.POINTER(u), C.POINTER(sz)],

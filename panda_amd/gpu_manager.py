@@ -227,8 +227,8 @@ def _vp(d) -> C.c_void_p:
 class _Buffers:
     """What one call takes from the library -- device, pool and pinned buffers, events -- released on every way out: in reverse order,
     each release attempted whatever the others return, an exception already on its way never replaced; a release that fails on an
-    otherwise clean exit raises CreateContextError.  The only place in this file that allocates or frees (deinit, PandaSparseMatrix.free
-    and PandaKzgOpenAll.close release what keep() handed over).  tests/test_gpu_manager_buffers.py runs every wrapper over it."""
+    otherwise clean exit raises CreateContextError.  The only place in this file that allocates or frees (deinit, PandaSparseMatrix.free,
+    PandaKzgOpenAll.close and PandaPoseidon.close release what keep() handed over).  tests/test_gpu_manager_buffers.py runs every wrapper over it."""
 
     def __init__(self, gm: "PandaGpuManager | None" = None):
         self.gm, self.lib, self._owned = gm, ffi.load(), []
@@ -1016,3 +1016,102 @@ class PandaKzgOpenAll:
             if d:
                 lib.panda_free(d)
             setattr(self, name, C.c_void_p())
+
+
+class PandaPoseidon:
+    """Additive: Poseidon over a scalar field (0 BN254 Fr, 1 BLS12-377 Fr, 2 BLS12-381 Fr) with one parameter set kept resident on the
+    device: the permutation, the sponge hash and the Merkle tree of panda_poseidon_*.  `mds` is a (t, t, 8) and `round_constants` a
+    (full_rounds + partial_rounds, t, 8) uint32 array of Montgomery-form elements; the width t is the matrix's.  A `tag` is 0 or one
+    Montgomery-form element (8 uint32).  Every method is ONE library call on device copies of its arguments; host arrays are not changed.
+    close() gives the table back."""
+
+    def __init__(self, gm: PandaGpuManager, round_constants, mds, alpha: int, full_rounds: int, partial_rounds: int, field: int = 0):
+        m = np.ascontiguousarray(mds, np.uint32)
+        if m.ndim != 3 or m.shape[0] != m.shape[1] or m.shape[2] != 8:
+            raise PandaGpuError("InvalidLengthErr")
+        self.gm, self.field, self.width = gm, field, m.shape[0]
+        rc = np.ascontiguousarray(round_constants, np.uint32).reshape(-1, 8)
+        if len(rc) != (full_rounds + partial_rounds) * self.width:
+            raise PandaGpuError("InvalidLengthErr")
+        params = ffi.PoseidonParams(self.width, alpha, full_rounds, partial_rounds, rc.ctypes.data, m.ctypes.data)
+        self.handle = ffi.PandaPoseidon()
+        with _Buffers(gm) as b:
+            ffi.check(b.lib.panda_poseidon_create(field, C.byref(params), C.byref(self.handle)), "CreateContextError")
+            b._own(b.lib.panda_poseidon_destroy, self.handle)
+            per = C.c_uint(0)
+            ffi.check(b.lib.panda_poseidon_plan(3, 1, C.byref(per), None, None, None, None), "SchedulingErr")
+            self.per_workgroup = per.value
+            b.keep(self.handle)
+
+    @staticmethod
+    def _tag(tag) -> np.ndarray:
+        if isinstance(tag, int) and tag == 0:
+            return np.zeros(8, np.uint32)
+        t = np.ascontiguousarray(tag, np.uint32).reshape(-1)
+        if t.size != 8:
+            raise PandaGpuError("InvalidLengthErr")
+        return t
+
+    def _live(self):
+        if not self.handle.handle:
+            raise PandaGpuError("SchedulingErr")
+
+    def permute(self, states) -> np.ndarray:
+        """(n, t, 8) states -> (n, t, 8) permuted states"""
+        s = np.ascontiguousarray(states, np.uint32)
+        self._live()
+        if s.ndim != 3 or s.shape[0] == 0 or s.shape[1:] != (self.width, 8):
+            raise PandaGpuError("InvalidLengthErr")
+        with _Buffers(self.gm) as b:
+            d, _, _ = b.upload([s.reshape(-1, 8)])
+            ffi.check(b.lib.panda_poseidon_permute(self.handle, d, d, s.shape[0], self.gm.exec_stream.raw), "SchedulingErr")
+            return b.read(np.empty(s.shape, np.uint32), d)
+
+    def _hash(self, data: np.ndarray, n: int, length: int, msg_stride: int, elem_stride: int, tag) -> np.ndarray:
+        t = self._tag(tag)
+        with _Buffers(self.gm) as b:
+            d_in, _, _ = b.upload([data.reshape(-1, 8)])
+            d_out = b.device(n * FIELD_ELEMENT_LEN)
+            ffi.check(b.lib.panda_poseidon_hash(self.handle, d_in, length, msg_stride, elem_stride, _ptr(t), d_out, n, self.gm.exec_stream.raw), "SchedulingErr")
+            return b.read(np.empty((n, 8), np.uint32), d_out)
+
+    def hash(self, messages, tag=0) -> np.ndarray:
+        """(n, len, 8): n messages as rows -> (n, 8), the sponge's state[0] after the last chunk"""
+        m = np.ascontiguousarray(messages, np.uint32)
+        self._live()
+        if m.ndim != 3 or m.shape[0] == 0 or m.shape[1] == 0 or m.shape[2] != 8:
+            raise PandaGpuError("InvalidLengthErr")
+        return self._hash(m, m.shape[0], m.shape[1], m.shape[1], 1, tag)
+
+    def hash_columns(self, columns, tag=0) -> np.ndarray:
+        """(len, n, 8): message i is row i across the len column vectors, the layout the batched transforms leave -> (n, 8)"""
+        c = np.ascontiguousarray(columns, np.uint32)
+        self._live()
+        if c.ndim != 3 or c.shape[0] == 0 or c.shape[1] == 0 or c.shape[2] != 8:
+            raise PandaGpuError("InvalidLengthErr")
+        return self._hash(c, c.shape[1], c.shape[0], 1, c.shape[1], tag)
+
+    def merkle_tree(self, leaves, tag=0):
+        """(a^height, 8) leaves, a = t - 1 -> (nodes, root): the (n - 1) / (a - 1) inner nodes level by level from the bottom as an (m, 8)
+        array, and the root (8,), which is also the last node"""
+        lv = np.ascontiguousarray(leaves, np.uint32)
+        self._live()
+        a, n, height = self.width - 1, len(lv), 0
+        if lv.ndim != 2 or lv.shape[1] != 8 or a < 2 or n < a:
+            raise PandaGpuError("InvalidLengthErr")
+        while a ** height < n:
+            height += 1
+        nodes = C.c_uint64(0)
+        if a ** height != n or ffi.load().panda_poseidon_plan(self.width, height, None, C.byref(nodes), None, None, None):
+            raise PandaGpuError("InvalidLengthErr")
+        t, root = self._tag(tag), np.empty(8, np.uint32)
+        with _Buffers(self.gm) as b:
+            d_leaves, _, _ = b.upload([lv])
+            d_nodes = b.device(nodes.value * FIELD_ELEMENT_LEN)
+            ffi.check(b.lib.panda_poseidon_merkle_tree(self.handle, d_leaves, height, _ptr(t), d_nodes, _ptr(root), self.gm.exec_stream.raw), "SchedulingErr")
+            return b.read(np.empty((nodes.value, 8), np.uint32), d_nodes), root
+
+    def close(self):
+        if self.handle.handle:
+            ffi.load().panda_poseidon_destroy(self.handle)
+        self.handle = ffi.PandaPoseidon()
